@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: env steps/s of the batched simulator on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 Workload (BASELINE.json configs[2], the one the metric is quoted on): 65 536 parallel envs
 per GPU, single sender, per-env randomized bandwidth / latency / queue / loss over the ICML'19
@@ -12,13 +12,20 @@ collective inside the step; episode returns are all-gathered over RCCL when epis
 `--gpus N` run directly (no torchrun) starts the N ranks itself.
 
 Protocol: W warm-up steps, then K timed steps between barrier +
-synchronize, repeated `--repeats` times back to back; the line reports the MEDIAN run, every run's
-ms/step, and which steps of the 400-step episode each run covered (`window`).  The packet count per
-step grows over an episode (about 120 early, 180 on average, 230 late), so WHERE a window shorter than
-an episode sits decides what it measures: when K < 400 the script first runs one whole untimed-for-`value`
-episode with per-step HIP events (reported as `whole_episode`: the section-8d metric), then places the K timed
-steps -- after an untimed pre-roll -- on the stretch of the episode whose mean step time is closest to the
-episode's mean, so that `value` estimates the whole-episode rate; `roofline` is computed from the whole episode.
+synchronize; `value` and `ms_per_step` are those K steps' (with `--repeats R`, the MEDIAN of R runs
+back to back), `window` says which steps of the 400-step episode they covered.  `--dump-outputs DIR`
+writes what the last timed step returned (obs, reward, done) as DIR/<name>.npy.
+
+A plain run does only that.  `--full` adds everything else, in the same process: 3 repeats by default,
+HIP events around the two kernels on a sample of the timed steps (`median_run_kernel_ms`), `roofline`
+with counter passes over two more runs, `policy_in_loop`, `scaling_in_n`, `many_steps_per_call` (small
+batches), `async_groups` (`--groups`) and `cpu_baseline`.  The packet count per step grows over an
+episode (about 120 early, 180 on average, 230 late), so WHERE a window shorter than an episode sits
+decides what it measures: with `--full` and K < 400 the script first runs three whole episodes with
+HIP events (reported as `whole_episode`: the section-8d metric), then places the K timed steps -- after
+an untimed pre-roll -- on the stretch of the episode whose mean step time is closest to the episode's
+mean; `roofline` is computed from the whole episodes then.  A plain run's short window starts at
+episode step W.
 
 `--config 2|3|5` picks the BASELINE.json configuration (default 3 = the one the metric is quoted on): 2 = 4 096 envs
 on the fixed link (bw 200, 0.03 s, queue 5, no loss, rate0 60), 5 = 32 768 envs x 2 senders.
@@ -46,6 +53,24 @@ HBM_PEAK_GBPS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 # reads the record.
 B_FIXED_SEND, B_FIXED_RETIRE, B_PACKET_HALF = 120, 330, 16
 REFERENCE_STEPS_PER_S_PER_CORE = 800.0   # the unmodified reference, SURVEY.md section 6 (build container)
+DUMP_BYTES = 64 << 20   # --dump-outputs writes at most this much, over all ranks
+
+
+def dump_outputs(out_dir, arrays, rank=0, world=1, budget=DUMP_BYTES):
+    """Writes `arrays` (numpy, first axis = env) as out_dir/<name>.npy, or <name>_rank<r>.npy with several ranks.  If they
+    are larger than this rank's share of `budget`, the same seeded sample of env rows is taken from each, and the sampled
+    env indices are written as env_index.npy (float64)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(next(iter(arrays.values())))
+    row_bytes = sum(a.nbytes for a in arrays.values()) // max(1, n)
+    share = budget // world - 1024 * (len(arrays) + 1)   # (room for the .npy headers)
+    if n * row_bytes > share:
+        keep = np.sort(np.random.RandomState(0).choice(n, share // (row_bytes + 8), replace=False))
+        arrays = dict({k: a[keep] for k, a in arrays.items()}, env_index=keep.astype(np.float64))
+    suffix = "_rank%d" % rank if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 def spawn_ranks(args):
@@ -109,7 +134,7 @@ def pmc_passes(config, timeout_s=150):
         for counter in ("FETCH_SIZE", "WRITE_SIZE"):
             d = os.path.join(tmp, counter.lower())
             cmd = [exe, "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", d, "-o", "p", "--", sys.executable,
-                   os.path.abspath(__file__), "--config", str(config), "--steps", "400", "--warmup", "20", "--repeats", "1",
+                   os.path.abspath(__file__), "--full", "--config", str(config), "--steps", "400", "--warmup", "20", "--repeats", "1",
                    "--no-cpu-baseline", "--no-pmc", "--no-policy", "--no-scaling"]
             try:
                 r = subprocess.run(cmd, cwd="/tmp", env=env, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL, timeout=timeout_s)
@@ -399,7 +424,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=2000, help="timed steps per run (5 episodes by default)")
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--repeats", type=int, default=3, help="timed runs, back to back; the line reports the median")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="timed runs, back to back; the line reports the median (default 1, with --full 3)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything besides the headline too (see the module docstring); the --no-* options, --cpu-seconds, "
+                         "--groups and --event-stride apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the obs / reward / done of the last timed step as DIR/<name>.npy (float32; at most 64 MB in all, "
+                         "a fixed sample of envs beyond that)")
     ap.add_argument("--envs", type=int, default=0, help="envs per GPU (default: the configuration's size)")
     ap.add_argument("--config", type=int, default=3, choices=(2, 3, 5),
                     help="BASELINE.json configuration: 3 (default) = 65 536 envs, randomized links, 1 sender; 2 = 4 096 envs on the "
@@ -416,10 +448,10 @@ def main():
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the two rocprofv3 counter passes that measure roofline.traffic (HBM bytes per launch)")
     ap.add_argument("--groups", type=int, default=0,
-                    help="also measure the same envs as this many independent groups on their own streams "
+                    help="with --full, also measure the same envs as this many independent groups on their own streams "
                          "(supplementary field async_groups)")
     ap.add_argument("--event-stride", type=int, default=7,
-                    help="HIP events around the two kernels on every this-many-th timed step (recording an event costs the "
+                    help="--full: HIP events around the two kernels on every this-many-th timed step (recording an event costs the "
                          "stream ~4.5 us, three per step are 7 %% of a step of config 3: the timed region carries them on a "
                          "sample of its steps -- 7 is coprime to the episode length, so every episode phase is sampled over a run -- "
                          "1 = every step)")
@@ -435,6 +467,8 @@ def main():
     ap.add_argument("--share-device", action="store_true",
                     help="testing only: every rank uses cuda:0 (lets the N > 1 path run on a 1-GPU box with gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(spawn_ranks(args))
@@ -460,7 +494,9 @@ def main():
     cfg = args.config
     N = args.envs or {2: 4096, 3: 65536, 5: 32768}[cfg]
     S = 2 if cfg == 5 else 1
-    K, W, R = args.steps, args.warmup, max(1, args.repeats)
+    full = args.full
+    K, W = args.steps, args.warmup
+    R = max(1, args.repeats if args.repeats is not None else (3 if full else 1))
     env = pcc_rl_amd.BatchedNetworkEnv(N, device=dev, seed=0, env_gid_base=pdist.env_gid_base(rank, N), n_senders=S,
                                        link_params=(200.0, 0.03, 5.0, 0.0, 60.0) if cfg == 2 else None,   # ns:459-464
                                        auto_reset=True, ring_capacity=args.ring_capacity, max_steps=args.max_steps,
@@ -499,23 +535,24 @@ def main():
         if ev is not None:
             ev[0].record()
         if fused:
-            env.step(actions[t % pool])
+            res = env.step(actions[t % pool])
         else:
             env.step_send(actions[t % pool])
         if ev is not None:
             ev[1].record()
         if not fused:
-            env.step_retire()
+            res = env.step_retire()
         if ev is not None:
             ev[2].record()
         if world > 1 and (t + 1) % max_steps == 0:
             # the only inter-GPU traffic on this path: episode returns, once per episode
             pdist.gather_episode_returns(env.episode_returns().to(torch.float32), out=gather_buf)
             returns_gathered += 1
+        return res
 
     t_global = 0
     whole = None
-    if K < max_steps and not args.stagger:
+    if full and K < max_steps and not args.stagger:
         # ---- whole episodes first (the section-8d metric), timed in segments of 5 steps: where in the episode do K steps
         # take the episode-mean time per step?  (All ranks do the same work; rank 0's times place the window.)
         # (episodes differ -- a handful of envs whose queue limit sits just above a power of two send on the slow exact
@@ -578,12 +615,13 @@ def main():
         t_global += 1
 
     runs = []
-    # HIP events on the launch stream (torch's current stream IS the stream the library launches on); all of them are
-    # made before the first run and the packet counters stay on the device until the last one is over, so that the GPU
+    # --full: HIP events on the launch stream (torch's current stream IS the stream the library launches on); all of them
+    # are made before the first run and the packet counters stay on the device until the last one is over, so that the GPU
     # does not sit idle (and clock down) between the warm-up steps and a timed region that may be only a few ms long
     ES = max(1, args.event_stride)
-    all_ev = [[[torch.cuda.Event(enable_timing=True) for _ in range(3)] if k % ES == 0 else None for k in range(K)] for _ in range(R)]
-    sent_marks = [env.state("total_sent").sum()]
+    all_ev = [[[torch.cuda.Event(enable_timing=True) for _ in range(3)] if full and k % ES == 0 else None for k in range(K)]
+              for _ in range(R)]
+    sent_marks = [env.state("total_sent").sum()] if full else None
     for r in range(R):
         ev = all_ev[r]
         first = t_global
@@ -592,18 +630,26 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for k in range(K):
-            one_step(t_global, ev[k] if k % ES == 0 else None)
+            last = one_step(t_global, ev[k])
             t_global += 1
         torch.cuda.synchronize()
         if world > 1:
             dist.barrier()
         elapsed = time.perf_counter() - t0
-        sent_marks.append(env.state("total_sent").sum())
+        if full:
+            sent_marks.append(env.state("total_sent").sum())
         runs.append({"elapsed": elapsed, "first_step": first})
+    if args.dump_outputs:
+        # what the caller of the timed path received from its last step (the env's own buffers: copied before any other step)
+        obs, reward, done, _ = last
+        dump_outputs(args.dump_outputs, {"obs": obs.float().cpu().numpy(), "reward": reward.float().cpu().numpy(),
+                                         "done": done.float().cpu().numpy()}, rank, world)
     for r in range(R):
         ev, first = all_ev[r], runs[r]["first_step"]
         runs[r]["per_rank_ms_per_step"] = [1e3 * v / K for v in pdist.gather_floats(runs[r]["elapsed"], device=dev)]
         runs[r]["elapsed"] = pdist.max_over_ranks(runs[r]["elapsed"], device=dev)     # MAX over ranks (bench contract)
+        if not full:
+            continue
         runs[r]["packets"] = float((sent_marks[r + 1] - sent_marks[r]).item())
         # steps that also ran the episode-boundary reset kernels are kept out of the retire average
         timed_k = [k for k in range(K) if k % ES == 0]   # the steps that carry events
@@ -615,7 +661,7 @@ def main():
         runs[r]["event_steps"] = len(timed_k)
         runs[r]["first_steps_ms"] = [ev[k][0].elapsed_time(ev[k][2]) for k in timed_k[:6]]
     many = None
-    if small and world == 1 and not args.stagger:
+    if full and small and world == 1 and not args.stagger:
         # a small batch: one step is a 25 us launch, less than a trip around the Python loop above.  Supplementary: the same K
         # steps queued by ONE library call (pcc_step_many: the loop runs in C); `value` stays the one-call-per-step figure
         acts_many = torch.stack([actions[(t_global + k) % pool] for k in range(K)])
@@ -629,7 +675,7 @@ def main():
                 "note": "the same steps queued from C by one pcc_step_many call (open loop: actions pre-computed); supplementary"}
     if not os.environ.get("PCC_BENCH_IGNORE_FLAGS"):   # experiments only: an overflowed ring means invalid results
         env.check_flags()
-    restart_stats = env.restart_stats() if args.stagger else None
+    restart_stats = env.restart_stats() if full and args.stagger else None
     fused_steps = env.fused_steps()
     env.close()
     coll = pdist.collective_info()
@@ -641,33 +687,10 @@ def main():
     if rank == 0:
         order = sorted(range(R), key=lambda r: runs[r]["elapsed"])
         med = runs[order[R // 2]]
+        # `value` / `ms_per_step` / `timed_steps` / `repeats` / `runs_ms_per_step` describe the K timed steps: value = envs x
+        # timed_steps / (ms_per_step x timed_steps), the median of the repeats, the MAX over ranks
         value = world * N * K / med["elapsed"]
         ms_per_step = 1e3 * med["elapsed"] / K
-        window_fields = None
-        # `value` / `ms_per_step` / `timed_steps` / `repeats` / `runs_ms_per_step` describe ONE measurement: value = envs x timed_steps /
-        # (ms_per_step x timed_steps).  `steps` stays the K the caller asked for (the bench contract echoes its arguments).
-        timed_steps, timed_repeats, timed_runs = K, R, [1e3 * r["elapsed"] / K for r in runs]
-        if whole is not None:
-            # fewer timed steps than an episode: the K-step window has no episode boundary inside, and SURVEY.md section 8d's
-            # metric includes the auto-resets -- so `value` is the whole episodes' figure (three 400-step episodes with their
-            # boundary resets, timed by this run just before the window), and the window is reported next to it
-            window_fields = {"value": value, "ms_per_step": ms_per_step, "steps": K, "repeats": R,
-                             "runs_ms_per_step": [1e3 * r["elapsed"] / K for r in runs],
-                             "note": "the %d timed steps after the warm-up (the bench contract's K), placed where an episode has its mean "
-                                     "step time; no episode boundary inside" % K}
-            value, ms_per_step = whole["value"], whole["ms_per_step"]
-            timed_steps, timed_repeats, timed_runs = whole["episodes"] * max_steps, 1, [whole["ms_per_step"]]
-        pk_per_step = med["packets"] / (N * K)
-        send_ms, retire_ms = med["send_ms"], med["retire_ms"]
-        roof_src = "the timed steps"
-        if whole is not None:   # the roofline of a short run is the whole episode's (the timed window is K steps of it)
-            pk_roof, send_ms, retire_ms = whole["packets_per_env_step"], whole["send_ms"], whole["retire_ms"]
-            roof_src = "the whole episodes run before the timed steps (whole_episode)"
-        else:
-            pk_roof = pk_per_step
-        # (two senders: the fixed bytes of section 8d once per sender)
-        send_bytes = N * (B_FIXED_SEND * S + B_PACKET_HALF * pk_roof)
-        retire_bytes = N * (B_FIXED_RETIRE * S + B_PACKET_HALF * pk_roof)
         if args.stagger:
             window = {"episode_steps": "all phases at once (--stagger): every step sees the episode-average load"}
         else:
@@ -677,18 +700,16 @@ def main():
                       "covers_whole_episodes": K % max_steps == 0,
                       "note": None if K >= max_steps else
                       "steps < one 400-step episode: packets per step grow over an episode (about 120 early, 180 on average, "
-                      "230 late); the window was placed (untimed pre-roll) where a whole episode run just before had its mean "
-                      "step time within %d steps -- `whole_episode` is that episode's own figure" % (W + K)}
+                      "230 late)" + ("; the window was placed (untimed pre-roll) where a whole episode run just before had its mean "
+                                     "step time within %d steps -- `whole_episode` is that episode's own figure" % (W + K) if whole is not None
+                                     else "; the window starts after the warm-up steps (--full places it where an episode has its "
+                                          "mean step time)")}
         out = {
             "metric": "env steps/sec (whole node) at 64k parallel envs",
             "value": value, "unit": "env steps/s", "n_gpus": world, "steps": K, "warmup": W,
-            "ms_per_step": ms_per_step, "timed_steps": timed_steps, "higher_is_better": True, "scaling": "weak",
+            "ms_per_step": ms_per_step, "timed_steps": K, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "repeats": timed_repeats, "runs_ms_per_step": timed_runs,
-            "median_run_kernel_ms": {"send": med["send_ms"], "retire": med["retire_ms"], "first_steps": med["first_steps_ms"],
-                                     "steps_with_events": med["event_steps"], "event_stride": ES,
-                                     "note": "HIP events around the two kernels on every event_stride-th timed step (an event record "
-                                             "costs the stream ~4.5 us; three on every step are 7 % of a step of config 3)"},
+            "repeats": R, "runs_ms_per_step": [1e3 * r["elapsed"] / K for r in runs],
             "spread": (max(r["elapsed"] for r in runs) - min(r["elapsed"] for r in runs)) / med["elapsed"],
             "window": window,
             "code": code_stamp(),
@@ -697,112 +718,124 @@ def main():
                                                 3: "1 sender, per-env randomized bw/latency/queue/loss (ICML'19 ranges)",
                                                 5: "2 senders on one bottleneck, per-env randomized links (ICML'19 ranges)"}[cfg],
                                        ", episode phases staggered" if args.stagger else "")),
-                       "baseline_config": cfg, "envs_per_gpu": N, "senders": S, "packets_per_env_step": pk_per_step,
+                       "baseline_config": cfg, "envs_per_gpu": N, "senders": S,
                        "episode_return_allgathers": returns_gathered},
         }
+        out["config"]["step_launches"] = ("one (step_small_kernel)" if small else "one (step_fused_kernel: an env's retire half follows its own send "
+                                          "half inside the launch); %d of this handle's steps ran that way, the others -- the step after "
+                                          "each reset, steps out of lockstep -- as send + retire launches" % fused_steps if fused else
+                                          "two (send_kernel, retire_kernel)")
         # what proves the multi-GPU line: the process group's own world size and backend (n_gpus above is the launcher's), the
         # RCCL version, every rank's own time for the timed steps (value uses their MAX), where each rank was pinned
         out["distributed"] = {"backend": coll["backend"], "dist_world_size": coll["dist_world_size"], "rccl_version": coll["rccl_version"],
                               "per_rank_ms_per_step": med.get("per_rank_ms_per_step"), "rank_cpu_binding": numa_all,
                               "launcher": "torchrun" if os.environ.get("TORCHELASTIC_RUN_ID") else "plain"}
-        if window_fields is not None:
-            out["timed_window"] = window_fields
-            out["value_source"] = ("whole_episode: %d whole %d-step episodes with their boundary resets (timed_steps = %d, one pass, MAX over "
-                                   "ranks), run and timed before the %d-step window (--steps < one episode); the K-step window with its own "
-                                   "repeats is `timed_window`" % (whole["episodes"], max_steps, whole["episodes"] * max_steps, K))
-        if whole is not None:
-            out["whole_episode"] = dict(whole, unit="env steps/s", steps=whole["episodes"] * max_steps,
-                                        note="%d whole %d-step episodes run before the timed steps (a boundary event every 5 steps, the "
-                                             "kernels' own events on every 14th): the section-8d metric and, with --steps below one "
-                                             "episode, the line's `value`; the K-step window (`timed_window`) sits at episode step "
-                                             "window_start + warmup of the next episode" % (whole["episodes"], max_steps))
-        send_gbps = send_bytes / (send_ms * 1e-3) / 1e9
-        retire_gbps = retire_bytes / (retire_ms * 1e-3) / 1e9
-        both = (send_bytes + retire_bytes) / ((send_ms + retire_ms) * 1e-3) / 1e9
-        if fused:   # one kernel: its bytes are both halves', its time is what the first event pair bracketed
-            send_bytes, retire_bytes = send_bytes + retire_bytes, 0.0
-            send_gbps = send_bytes / (send_ms * 1e-3) / 1e9
-            retire_gbps, retire_ms = 0.0, 0.0
-            both = send_gbps
-        out["roofline"] = {"bound": "hbm", "kernel": ("step_small_kernel<%d, false>" if small else "step_fused_kernel<%d, false>" if fused else "send_kernel<%d, false>") % S, "achieved": send_gbps,
-                           "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": send_gbps / HBM_PEAK_GBPS,
-                           "traffic": None, "kernel_ms": send_ms, "algorithmic_bytes_per_launch": send_bytes,
-                           "measured_over": roof_src,
-                           "other_kernels": [] if fused else [{"kernel": "retire_kernel<%d, false>" % S, "achieved": retire_gbps,
-                                              "frac": retire_gbps / HBM_PEAK_GBPS, "kernel_ms": retire_ms,
-                                              "algorithmic_bytes_per_launch": retire_bytes}],
-                           "whole_step": {"achieved": both, "frac": both / HBM_PEAK_GBPS}}
-        if not fused and not small and S == 1:
-            # what the dominant kernel's traffic IS: scattered 16-byte ring appends, one per packet.  The chip absorbs ~205 G of
-            # them per second (3.3 TB/s) whatever the coding -- measured by tools/microbench/lane_round (variants 2 / 7 / 8:
-            # one record per request, four per request through LDS, four per request by a drain wavefront) and round 4's
-            # store_bench4 -- and the send launch's busy phase (its first ~55 us, before the serial tail) runs at 196 G/s.
-            out["roofline"]["scattered_record_ceiling"] = {
-                "records_per_s": 2.05e11, "GB/s": 3280.0, "frac_of_hbm_peak": 3280.0 / HBM_PEAK_GBPS,
-                "launch_average_records_per_s": N * pk_roof / (send_ms * 1e-3),
-                "launch_average_frac_of_ceiling": N * pk_roof / (send_ms * 1e-3) / 2.05e11,
-                "note": "supplementary: the rate at which the memory system takes scattered 16-byte records = PARTIAL-LINE writes "
-                        "(profiles/r06_store_bw.txt: 3.0-3.25 TB/s; whole lines, dense or scattered, 5.1-6.6 TB/s; "
-                        "profiles/r06_lane_round_microbench.txt); only the lane rounds' records (45 % of a launch's) are written that "
-                        "way since round 6, the wave path's leave as whole lines; the launch average includes the serial tail of the "
-                        "longest lane-round items (profiles/r06_send_tail.json), during which that bandwidth idles"}
-        # HBM traffic from the counters: measured now, by two profiled runs of this script (unless --no-pmc / not one GPU);
-        # else the newest committed summary, labelled as such
-        kname = out["roofline"]["kernel"]
-        pmc, src, why = None, None, "--no-pmc"
-        if not args.no_pmc and world == 1:
-            pmc, why = pmc_passes(cfg)
-            src = "measured by this run"
-        live = pmc is not None
-        if pmc is None and N == 65536 and cfg == 3:
-            pmc, src = pmc_traffic()
-        if pmc and kname in pmc and pmc[kname].get("launches", 0) >= 50 and "hbm_bytes_per_launch" in pmc[kname]:
-            out["roofline"]["traffic"] = pmc[kname]["hbm_bytes_per_launch"]
-            out["roofline"]["traffic_over_algorithmic"] = pmc[kname].get("traffic_over_algorithmic")
-            what = ("2 x FETCH_SIZE + WRITE_SIZE (KB units x 1024; the factor 2 is this repo's calibration, "
-                    "profiles/r02_pmc_calibration.json), rocprofv3 --pmc in separate passes")
-            if live:
-                out["roofline"]["traffic_source"] = (src + ": " + what + " over two more runs of this script on this GPU, one whole "
-                                                     "episode each (after 20 warm-up steps); traffic_over_algorithmic compares it with "
-                                                     "THAT window's algorithmic bytes")
+        if full:
+            out["median_run_kernel_ms"] = {"send": med["send_ms"], "retire": med["retire_ms"], "first_steps": med["first_steps_ms"],
+                                           "steps_with_events": med["event_steps"], "event_stride": ES,
+                                           "note": "HIP events around the two kernels on every event_stride-th timed step (an event "
+                                                   "record costs the stream ~4.5 us; three on every step are 7 % of a step of config 3)"}
+            pk_per_step = med["packets"] / (N * K)
+            out["config"]["packets_per_env_step"] = pk_per_step
+            send_ms, retire_ms = med["send_ms"], med["retire_ms"]
+            roof_src = "the timed steps"
+            if whole is not None:   # the roofline of a short run is the whole episode's (the timed window is K steps of it)
+                pk_roof, send_ms, retire_ms = whole["packets_per_env_step"], whole["send_ms"], whole["retire_ms"]
+                roof_src = "the whole episodes run before the timed steps (whole_episode)"
             else:
-                out["roofline"]["traffic_source"] = (src + " (the counter passes of this run: " + str(why) + "): " + what + " of a SEPARATE "
-                                                     "profiled run of this script (code at commit " + str(pmc.get("_commit", "?")) + ") over " +
-                                                     str(pmc.get("_window", "steps 20..120 of an episode")) + "; compare it with that "
-                                                     "window's algorithmic bytes (in the profile), not this run's")
-            for other in out["roofline"].get("other_kernels", []):
-                if other["kernel"] in pmc and pmc[other["kernel"]].get("launches", 0) >= 50 and "hbm_bytes_per_launch" in pmc[other["kernel"]]:
-                    other["traffic"] = pmc[other["kernel"]]["hbm_bytes_per_launch"]
-                    other["traffic_over_algorithmic"] = pmc[other["kernel"]].get("traffic_over_algorithmic")
-        elif why:
-            out["roofline"]["traffic_source"] = "none: " + str(why)
-        if restart_stats is not None:
-            out["restarts_out_of_lockstep"] = restart_stats
-        out["config"]["step_launches"] = ("one (step_small_kernel)" if small else "one (step_fused_kernel: an env's retire half follows its own send "
-                                          "half inside the launch); %d of this handle's steps ran that way, the others -- the step after "
-                                          "each reset, steps out of lockstep -- as send + retire launches" % fused_steps if fused else
-                                          "two (send_kernel, retire_kernel)")
-        if many is not None:
-            out["many_steps_per_call"] = many
-        if world == 1 and cfg == 3 and not args.stagger and not args.no_policy and N >= 8192:
-            try:
-                out["policy_in_loop"] = policy_in_loop(pcc_rl_amd, torch, N, dev)
-            except Exception as e:   # (supplementary: never in the way of the line)
-                out["policy_in_loop"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and cfg == 3 and not args.stagger and not args.no_scaling and N == 65536 and not fused:
-            pts = scaling_in_n(pcc_rl_amd, torch, dev, max_steps=max_steps)
-            head = {"envs": N, "value": value, "unit": "env steps/s", "ms_per_step": ms_per_step, "send_ms": send_ms, "retire_ms": retire_ms,
-                    "packets_per_env_step": pk_roof, "note": "the line's own figures"}
-            out["scaling_in_n"] = {"points": [head] + pts,
-                                   "note": "envs per GPU beyond BASELINE's 65 536 (same links, same action law, one whole episode each after 40 "
-                                           "warm-up steps; supplementary): the two launches of a step are as long as their longest work "
-                                           "items, so a larger batch costs less than proportionally -- what a trainer should run per GPU"}
-        if world == 1 and args.groups > 1:
-            out["async_groups"] = async_groups(pcc_rl_amd, torch, N, dev, K, W, args.groups)
-        if not args.no_cpu_baseline and world == 1:
-            out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
-        elif world == 1:
-            out["cpu_baseline"] = None
+                pk_roof = pk_per_step
+            # (two senders: the fixed bytes of section 8d once per sender)
+            send_bytes = N * (B_FIXED_SEND * S + B_PACKET_HALF * pk_roof)
+            retire_bytes = N * (B_FIXED_RETIRE * S + B_PACKET_HALF * pk_roof)
+            if whole is not None:
+                out["whole_episode"] = dict(whole, unit="env steps/s", steps=whole["episodes"] * max_steps,
+                                            note="%d whole %d-step episodes with their boundary resets, run before the timed steps (a "
+                                                 "boundary event every 5 steps, the kernels' own events on every 14th): the section-8d "
+                                                 "metric; the K timed steps sit at episode step window_start + warmup of the next "
+                                                 "episode" % (whole["episodes"], max_steps))
+            send_gbps = send_bytes / (send_ms * 1e-3) / 1e9
+            retire_gbps = retire_bytes / (retire_ms * 1e-3) / 1e9
+            both = (send_bytes + retire_bytes) / ((send_ms + retire_ms) * 1e-3) / 1e9
+            if fused:   # one kernel: its bytes are both halves', its time is what the first event pair bracketed
+                send_bytes, retire_bytes = send_bytes + retire_bytes, 0.0
+                send_gbps = send_bytes / (send_ms * 1e-3) / 1e9
+                retire_gbps, retire_ms = 0.0, 0.0
+                both = send_gbps
+            out["roofline"] = {"bound": "hbm", "kernel": ("step_small_kernel<%d, false>" if small else "step_fused_kernel<%d, false>" if fused else "send_kernel<%d, false>") % S, "achieved": send_gbps,
+                               "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": send_gbps / HBM_PEAK_GBPS,
+                               "traffic": None, "kernel_ms": send_ms, "algorithmic_bytes_per_launch": send_bytes,
+                               "measured_over": roof_src,
+                               "other_kernels": [] if fused else [{"kernel": "retire_kernel<%d, false>" % S, "achieved": retire_gbps,
+                                                  "frac": retire_gbps / HBM_PEAK_GBPS, "kernel_ms": retire_ms,
+                                                  "algorithmic_bytes_per_launch": retire_bytes}],
+                               "whole_step": {"achieved": both, "frac": both / HBM_PEAK_GBPS}}
+            if not fused and not small and S == 1:
+                # what the dominant kernel's traffic IS: scattered 16-byte ring appends, one per packet.  The chip absorbs ~205 G of
+                # them per second (3.3 TB/s) whatever the coding -- measured by tools/microbench/lane_round (variants 2 / 7 / 8:
+                # one record per request, four per request through LDS, four per request by a drain wavefront) and round 4's
+                # store_bench4 -- and the send launch's busy phase (its first ~55 us, before the serial tail) runs at 196 G/s.
+                out["roofline"]["scattered_record_ceiling"] = {
+                    "records_per_s": 2.05e11, "GB/s": 3280.0, "frac_of_hbm_peak": 3280.0 / HBM_PEAK_GBPS,
+                    "launch_average_records_per_s": N * pk_roof / (send_ms * 1e-3),
+                    "launch_average_frac_of_ceiling": N * pk_roof / (send_ms * 1e-3) / 2.05e11,
+                    "note": "supplementary: the rate at which the memory system takes scattered 16-byte records = PARTIAL-LINE writes "
+                            "(profiles/r06_store_bw.txt: 3.0-3.25 TB/s; whole lines, dense or scattered, 5.1-6.6 TB/s; "
+                            "profiles/r06_lane_round_microbench.txt); only the lane rounds' records (45 % of a launch's) are written that "
+                            "way since round 6, the wave path's leave as whole lines; the launch average includes the serial tail of the "
+                            "longest lane-round items (profiles/r06_send_tail.json), during which that bandwidth idles"}
+            # HBM traffic from the counters: measured now, by two profiled runs of this script (unless --no-pmc / not one GPU);
+            # else the newest committed summary, labelled as such
+            kname = out["roofline"]["kernel"]
+            pmc, src, why = None, None, "--no-pmc"
+            if not args.no_pmc and world == 1:
+                pmc, why = pmc_passes(cfg)
+                src = "measured by this run"
+            live = pmc is not None
+            if pmc is None and N == 65536 and cfg == 3:
+                pmc, src = pmc_traffic()
+            if pmc and kname in pmc and pmc[kname].get("launches", 0) >= 50 and "hbm_bytes_per_launch" in pmc[kname]:
+                out["roofline"]["traffic"] = pmc[kname]["hbm_bytes_per_launch"]
+                out["roofline"]["traffic_over_algorithmic"] = pmc[kname].get("traffic_over_algorithmic")
+                what = ("2 x FETCH_SIZE + WRITE_SIZE (KB units x 1024; the factor 2 is this repo's calibration, "
+                        "profiles/r02_pmc_calibration.json), rocprofv3 --pmc in separate passes")
+                if live:
+                    out["roofline"]["traffic_source"] = (src + ": " + what + " over two more runs of this script on this GPU, one whole "
+                                                         "episode each (after 20 warm-up steps); traffic_over_algorithmic compares it with "
+                                                         "THAT window's algorithmic bytes")
+                else:
+                    out["roofline"]["traffic_source"] = (src + " (the counter passes of this run: " + str(why) + "): " + what + " of a SEPARATE "
+                                                         "profiled run of this script (code at commit " + str(pmc.get("_commit", "?")) + ") over " +
+                                                         str(pmc.get("_window", "steps 20..120 of an episode")) + "; compare it with that "
+                                                         "window's algorithmic bytes (in the profile), not this run's")
+                for other in out["roofline"].get("other_kernels", []):
+                    if other["kernel"] in pmc and pmc[other["kernel"]].get("launches", 0) >= 50 and "hbm_bytes_per_launch" in pmc[other["kernel"]]:
+                        other["traffic"] = pmc[other["kernel"]]["hbm_bytes_per_launch"]
+                        other["traffic_over_algorithmic"] = pmc[other["kernel"]].get("traffic_over_algorithmic")
+            elif why:
+                out["roofline"]["traffic_source"] = "none: " + str(why)
+            if restart_stats is not None:
+                out["restarts_out_of_lockstep"] = restart_stats
+            if many is not None:
+                out["many_steps_per_call"] = many
+            if world == 1 and cfg == 3 and not args.stagger and not args.no_policy and N >= 8192:
+                try:
+                    out["policy_in_loop"] = policy_in_loop(pcc_rl_amd, torch, N, dev)
+                except Exception as e:   # (supplementary: never in the way of the line)
+                    out["policy_in_loop"] = {"error": "%s: %s" % (type(e).__name__, e)}
+            if world == 1 and cfg == 3 and not args.stagger and not args.no_scaling and N == 65536 and not fused:
+                pts = scaling_in_n(pcc_rl_amd, torch, dev, max_steps=max_steps)
+                head = {"envs": N, "value": value, "unit": "env steps/s", "ms_per_step": ms_per_step, "send_ms": send_ms, "retire_ms": retire_ms,
+                        "packets_per_env_step": pk_roof, "note": "the line's own figures"}
+                out["scaling_in_n"] = {"points": [head] + pts,
+                                       "note": "envs per GPU beyond BASELINE's 65 536 (same links, same action law, one whole episode each after 40 "
+                                               "warm-up steps; supplementary): the two launches of a step are as long as their longest work "
+                                               "items, so a larger batch costs less than proportionally -- what a trainer should run per GPU"}
+            if world == 1 and args.groups > 1:
+                out["async_groups"] = async_groups(pcc_rl_amd, torch, N, dev, K, W, args.groups)
+            if not args.no_cpu_baseline and world == 1:
+                out["cpu_baseline"] = cpu_baseline(args.cpu_seconds)
+            elif world == 1:
+                out["cpu_baseline"] = None
         print(json.dumps(out))
     if world > 1:
         dist.destroy_process_group()

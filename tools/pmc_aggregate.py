@@ -60,7 +60,7 @@ def aggregate(dirs, bench_line=None):
                 out[name]["algorithmic_bytes_per_launch"] = k["algorithmic_bytes_per_launch"]
                 if "hbm_bytes_per_launch" in out[name]:
                     out[name]["traffic_over_algorithmic"] = out[name]["hbm_bytes_per_launch"] / k["algorithmic_bytes_per_launch"]
-    out["_note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `python bench.py --steps 400 --warmup 20 "
+    out["_note"] = ("rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes over `python bench.py --full --steps 400 --warmup 20 "
                     "--repeats 1 --no-cpu-baseline` (one whole episode); counters are KB per dispatch.  hbm_bytes_per_launch = "
                     "2 x FETCH_SIZE + WRITE_SIZE: tools/pmc_calibrate.sh (profiles/r02_pmc_calibration.json) measured FETCH_SIZE at "
                     "exactly half of the fetched 128-byte lines for every read pattern of these kernels and WRITE_SIZE at 1.0 x (dense) "

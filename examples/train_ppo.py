@@ -25,9 +25,12 @@ def main():
     ap.add_argument("--arch", default="32,16")
     ap.add_argument("--gamma", type=float, default=0.99)
     ap.add_argument("--save", default="")
+    ap.add_argument("--policy-in-step", action="store_true",
+                    help="collect each horizon as one closed-loop call (pcc_rollout): the policy inside the env's launches")
     args = ap.parse_args()
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0)
-    agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon)
+    agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
+                policy_in_step=args.policy_in_step)
     t0 = time.perf_counter()
     for it in range(args.iters):
         s = agent.iterate()

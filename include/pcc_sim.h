@@ -249,6 +249,11 @@ enum { PCC_TUNE_ROUND_PACKETS = 2, PCC_TUNE_TAKEOVER_LANES = 3,
                                     dispatcher places the wave-path workgroups first otherwise).  Default 6 (send launch 0.0893 ->
                                     0.0864 ms at 65 536 envs); not applied to launches that carry restart items (out of lockstep: measured
                                     slower).  Speed only */,
+       PCC_TUNE_ROLLOUT_EPILOGUE = 36 /* pcc_rollout with work lists (one sender, the 32,16 policy): 1 = the policy in the epilogue
+                                    of the retire launch (the next action from the observation row it has just written: one launch
+                                    less per step); 0 (default) = the policy kernel and the two halves, launch by launch -- the epilogue
+                                    measured slower (retire launch 89 -> 149 us against a 39 us policy launch under the tracer,
+                                    DESIGN.md section 14).  Results do not depend on it. */,
        PCC_TUNE_FUSED_DEBUG = 31 /* fused step, experiments: bit 0 (1) = an agent-scope release (buffer_wbl2) in front of every publication,
                                     bit 2 (4) = no retire work before every env is sent (the halves one after the other inside the launch);
                                     default 0 */ };
@@ -337,11 +342,31 @@ int pcc_step(pcc_sim_t *sim, const void *actions, int actions_f64, float *obs_ou
  * envs than LIST_MIN_ENVS) whose episode boundaries the host knows runs the steps up to the next boundary inside ONE
  * launch -- the loop over the steps is on the device, a workgroup per 64 envs, no launch boundary between steps (config 2:
  * a step is a chain of dependent loads, and a launch boundary is a third of it); other batches are stepped launch by launch
- * from C.  For open-loop drivers: a policy in the loop needs the observation of every step and calls pcc_step.  On an error
+ * from C.  For open-loop drivers: a policy in the loop needs the observation of every step -- pcc_rollout.  On an error
  * the message says after how many steps the call stopped.  The reference has no counterpart (its step() is one Python call
  * per interval, ns:406). */
 int pcc_step_many(pcc_sim_t *sim, const void *actions, int actions_f64, int n_steps, float *obs_out, float *reward_out,
                   uint8_t *done_out, double *steps_out, int auto_reset, void *stream);
+
+/* Closed-loop stepping: n_steps steps, each with the actions the policy takes on the observation of the step before -- the
+ * policy of pcc_policy_act (include/pcc_policy.h: `params` is its parameter block, hidden sizes h1, h2).  The outputs are
+ * bit-identical to this loop, for t = 0 .. n_steps-1:
+ *     pcc_policy_act(obs_io[t], N*S, H*F, params, h1, h2, noise ? noise[t] : NULL, NULL, act[t], logp[t], value[t])
+ *     pcc_step(sim, act[t], 0, obs_io[t+1], reward[t], done[t], steps[t], auto_reset)
+ *   obs_io      [n_steps+1][N][S][H*F]: row 0 is read (the current observation), rows 1..n_steps are written
+ *   noise       [n_steps][N][S] standard-normal draws; NULL = deterministic (act = the mean)
+ *   act_out, logp_out, value_out  [n_steps][N][S]; reward_out, done_out, steps_out: pcc_step_many's shapes
+ * Every output but obs_io may be NULL (act_out NULL: the handle keeps the actions in two rows of its own).  With one sender and
+ * the reference's --arch 32,16 at an observation length pcc_policy_act has a kernel for, a small batch runs the policy inside
+ * the loop of the one-launch segments of pcc_step_many; at full size the policy goes into the epilogue of the retire launch
+ * when PCC_TUNE_ROLLOUT_EPILOGUE asks for it (measured slower: off by default, the steps launch by launch).  Other
+ * configurations (two senders, the event-loop build, other sizes, the one-launch step PCC_TUNE_FUSED) run the loop above as it
+ * reads.  PCC_EINVAL: the congestion-window mode (two actions per sender), NULL params / obs_io, n_steps < 1, a policy shape
+ * pcc_policy_act has no kernel for; PCC_ESTATE: what pcc_step refuses.  On an error the message says after how many steps the
+ * call stopped.  No reference counterpart (the reference's agent calls step() once per interval). */
+int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps, const float *noise, float *obs_io,
+                float *act_out, float *logp_out, float *value_out, float *reward_out, uint8_t *done_out, double *steps_out,
+                int auto_reset, void *stream);
 
 /*
  * The two halves of pcc_step as separate calls (pcc_step = pcc_step_send + pcc_step_retire with the

@@ -11,7 +11,7 @@ CSRC = os.path.join(HERE, "csrc")
 UNITS = ["pcc_sim.hip", "pcc_send.hip", "pcc_send_restart.hip", "pcc_retire.hip", "pcc_small.hip", "pcc_fused.hip", "pcc_noise_sorted.hip",
          "pcc_policy.hip", "pcc_ppo.hip"]
 SRCS = [os.path.join(CSRC, u) for u in UNITS]
-HEADERS = [os.path.join(CSRC, h) for h in ("pcc_dev.h", "pcc_kernels.h", "pcc_wave_pass.h", "pcc_send_item.h", "pcc_send_bodies.h", "pcc_retire_env.h")]
+HEADERS = [os.path.join(CSRC, h) for h in ("pcc_dev.h", "pcc_kernels.h", "pcc_wave_pass.h", "pcc_send_item.h", "pcc_send_bodies.h", "pcc_retire_env.h", "pcc_policy_dev.h")]
 INCLUDE = os.path.join(ROOT, "include")
 LIB_DIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIB_DIR, "libpcc_sim.so")

@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "pcc_policy.h"
+#include "pcc_policy_dev.h"
 
 namespace {
 
@@ -60,13 +61,8 @@ __global__ __launch_bounds__(256) void policy_act_kernel(const float *obs, int64
     if (value_out) value_out[i] = v;
 }
 
-// tanh(x) = 1 - 2 / (exp(2x) + 1) by the hardware's exp2 and reciprocal: absolute error ~1e-7, saturates cleanly -- the same
-// function the gradient kernel evaluates (pcc_ppo.hip: the rollout's and the update's forward agree), a fifth of libm's tanhf
-// in instructions (48 of them per network and env: half of the fixed kernel's time went into them)
-__device__ __forceinline__ float tanh_fast(float x) {
-    const float e = __expf(2.0f * x);
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
+// tanh_fast: pcc_policy_dev.h (shared with the rollout epilogue of the env's kernels, which must give this kernel's bits)
+using pcc::tanh_fast;
 
 // The reference's own sizes (--arch 32,16) with everything a compile-time constant: the hidden activations stay in
 // registers (the generic kernel above indexes z1[j] with a run-time j: scratch memory), the loops unroll.

@@ -21,11 +21,24 @@ namespace {
 // registers are free for the next workgroup as soon as ITS envs are done.
 constexpr int kRetireMaxPerBlock = kRetireBlock / 8;  // envs of a workgroup at 8 lanes per env
 
-template <int NS, bool NOISE>
+// The LDS of the policy epilogue (POLICY, pcc_rollout): kRetireMaxPerBlock envs' scratch, then the parameter block -- sized by
+// the launch
+__device__ __forceinline__ float *pol_lds() {
+    extern __shared__ float s_pol_dyn[];
+    return s_pol_dyn;
+}
+
+// retire_kernel<1, false, PolicyArgs> (pcc_rollout; one sender, not NOISE, never a warm-up interval): the policy epilogue -- after
+// an env's retire half its group computes the env's next action from the observation row it has just written
+// (pcc_policy_dev.h).  The instantiations without it (no trailing argument) are the kernels they were before it existed.
+__device__ __forceinline__ const PolicyArgs &pol_arg(const PolicyArgs &p) { return p; }
+
+template <int NS, bool NOISE, typename... Pol>
 __global__ __launch_bounds__(kRetireBlock, NS == 2 ? PCC_RETIRE_OCC2 : PCC_RETIRE_OCC) void retire_kernel(Dev D, int read_buf, int fill_buf, int warm,
                                                               uint32_t warm_mi, int last_warm, int gate, int restart, float *obs_out,
                                                               float *reward_out, uint8_t *done_out, double *steps_out,
-                                                              const void *actions, int actions_f64) {
+                                                              const void *actions, int actions_f64, Pol... pol) {
+    constexpr bool POLICY = sizeof...(Pol) > 0;
     if (gate && __hip_atomic_load(D.any_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != D.step_seq) return;
     __shared__ uint32_t s_env[kRetireMaxPerBlock], s_cls[kRetireMaxPerBlock], s_arrived;
     const uint32_t tid = threadIdx.x;
@@ -38,6 +51,10 @@ __global__ __launch_bounds__(kRetireBlock, NS == 2 ? PCC_RETIRE_OCC2 : PCC_RETIR
     const uint32_t lane = tid & (kWave - 1);
     if (tid == 0) s_arrived = 0u;
     if (tid < (uint32_t)kRetireMaxPerBlock) s_env[tid] = 0xFFFFFFFFu;
+    if constexpr (POLICY) {   // the parameter block, once per workgroup (12.3 KB at 30 observations)
+        float *w = pol_lds() + kRetireMaxPerBlock * kPolScratch;
+        for (int k = (int)tid; k < pol_arg(pol...).n_params; k += kRetireBlock) w[k] = pol_arg(pol...).params[k];
+    }
     __syncthreads();  // the workgroup's wavefronts start together: this one is free
     int64_t i = D.n;   // (beyond the envs: nothing)
     bool wide = false;  // this workgroup: 16 lanes per env
@@ -104,17 +121,25 @@ __global__ __launch_bounds__(kRetireBlock, NS == 2 ? PCC_RETIRE_OCC2 : PCC_RETIR
         g.shift = lane & ~15u;
         slot = tid / 16u;
         glead = g.lane == 0;
-        if (i < D.n)
+        if (i < D.n) {
             pred = retire_env<NS, NOISE, 16>(D, i, g, warm, warm_mi, last_warm, restart, obs_out, reward_out, done_out, steps_out,
                                              actions, actions_f64);
+            if constexpr (POLICY)
+                policy_group<16>(pol_arg(pol...), pol_lds() + kRetireMaxPerBlock * kPolScratch, pol_lds() + slot * kPolScratch, obs_out + i * D.HF,
+                                 i, D.n, g.lane, pol_arg(pol...).t0 + 1);
+        }
     } else {
         g.lane = tid & 7u;
         g.shift = lane & ~7u;
         slot = tid / 8u;
         glead = g.lane == 0;
-        if (i < D.n)
+        if (i < D.n) {
             pred = retire_env<NS, NOISE, 8>(D, i, g, warm, warm_mi, last_warm, restart, obs_out, reward_out, done_out, steps_out,
                                             actions, actions_f64);
+            if constexpr (POLICY)
+                policy_group<8>(pol_arg(pol...), pol_lds() + kRetireMaxPerBlock * kPolScratch, pol_lds() + slot * kPolScratch, obs_out + i * D.HF,
+                                i, D.n, g.lane, pol_arg(pol...).t0 + 1);
+        }
     }
     if (fill_buf < 0) return;  // warm-up intervals do not file (kernel-uniform)
     // ---- file the workgroup's envs in the class lists of the next send (see "work lists")
@@ -156,7 +181,13 @@ namespace pcc {
 
 void launch_retire(const Dev &d, bool noise, unsigned grid, hipStream_t st, int read_buf, int fill_buf, int warm, uint32_t warm_mi,
                    int last_warm, int gate, int restart, float *obs_out, float *reward_out, uint8_t *done_out, double *steps_out,
-                   const void *actions, int actions_f64) {
+                   const void *actions, int actions_f64, const PolicyArgs *pol) {
+    if (pol) {   // (the host only asks for it with one sender, no event loop, no warm-up interval)
+        const size_t lds = (size_t)(kRetireMaxPerBlock * kPolScratch + pol->n_params) * sizeof(float);
+        hipLaunchKernelGGL((retire_kernel<1, false, PolicyArgs>), dim3(grid), dim3(kRetireBlock), lds, st, d, read_buf, fill_buf, 0, 0u, 0, 0,
+                           restart, obs_out, reward_out, done_out, steps_out, nullptr, 0, *pol);
+        return;
+    }
 #define PCC_RT(NS_, NZ_)                                                                                                          \
     hipLaunchKernelGGL((retire_kernel<NS_, NZ_>), dim3(grid), dim3(kRetireBlock), 0, st, d, read_buf, fill_buf, warm, warm_mi, last_warm, \
                        gate, restart, obs_out, reward_out, done_out, steps_out, actions, actions_f64)

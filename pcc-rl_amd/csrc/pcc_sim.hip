@@ -6,6 +6,7 @@
 // src/common/sender_obs.py): SimulatedNetworkEnv.reset / step (ns:406-484) for N independent envs advanced one monitor
 // interval per step -- see pcc_dev.h for the formulation.
 #include "pcc_kernels.h"
+#include "pcc_policy.h"
 
 using namespace pcc;
 
@@ -83,6 +84,9 @@ struct pcc_sim {
     uint32_t fused_light_wgs;
     uint32_t fused_light_front;   // ... of which so many per partition are dispatched in FRONT of the wave-path workgroups
     unsigned long long fused_steps;  // steps that ran as one launch (pcc_debug_fused_steps)
+    int rollout_epilogue;   // PCC_TUNE_ROLLOUT_EPILOGUE: pcc_rollout at full size with the policy in the retire launch (1) or not (0)
+    float *roll_act;        // pcc_rollout without act_out: two rows of actions, used in turn
+    size_t roll_act_floats;
 };
 
 namespace {
@@ -226,8 +230,9 @@ int launch_send(pcc_sim_t *sim, int warm, uint32_t warm_mi, int gate, const void
 // RETIRE half; a launch that is not a warm-up interval also files every env in the work lists of the
 // next send (buffer sim->fill_buf, cleared by the send launch before it)
 // restart: envs that finish their episode in this launch are reset inside it and filed in the restart list
+// pol: the policy epilogue (pcc_rollout): every env's next action from the observation row this launch writes
 int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm, int gate, int restart, float *obs_out,
-                       float *reward_out, uint8_t *done_out, double *steps_out, hipStream_t st) {
+                       float *reward_out, uint8_t *done_out, double *steps_out, hipStream_t st, const PolicyArgs *pol = nullptr) {
     const Dev &d = sim->d;
     // workgroups: 8 envs each at 16 lanes per env, 16 at 8 lanes -- which envs go which way is decided on the device
     // (class counts), so the grid covers the worst case plus the one workgroup the split can leave partly filled
@@ -243,7 +248,7 @@ int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm
     const unsigned grid = (unsigned)(read >= 0 ? (int64_t)d.parts * (narrow_part + (int64_t)(sim->retire_grid_frac * (double)narrow_part) + 1) : narrow);
     const int fill = (warm || !lists) ? -1 : sim->fill_buf;
     launch_retire(d, false, grid, st, read, fill, warm, warm_mi, last_warm, gate, restart, obs_out, reward_out, done_out, steps_out,
-                  nullptr, 0);
+                  nullptr, 0, pol);
     const int rc = check_hip(hipGetLastError(), "retire kernel launch");
     if (rc == PCC_OK && !warm && lists) {
         sim->read_buf = sim->fill_buf;
@@ -660,6 +665,7 @@ void pcc_destroy(pcc_sim_t *sim) {
     if (sim->list_blob) (void)hipFree(sim->list_blob);
     if (sim->noise_blob) (void)hipFree(sim->noise_blob);
     if (sim->noise_out_blob) (void)hipFree(sim->noise_out_blob);
+    if (sim->roll_act) (void)hipFree(sim->roll_act);
 
     if (sim->state_blob) (void)hipFree(sim->state_blob);
     for (int c = 0; c < kMaxTiers; c++) {
@@ -813,6 +819,10 @@ int pcc_set_tuning(pcc_sim_t *sim, int key, double value) {
         case PCC_TUNE_LIGHT_FRONT:
             if (!(value >= 0.0 && value <= 65536.0)) return fail(PCC_EINVAL, "light_front out of range");
             sim->light_front = (uint32_t)value;
+            return PCC_OK;
+        case PCC_TUNE_ROLLOUT_EPILOGUE:
+            if (value != 0.0 && value != 1.0) return fail(PCC_EINVAL, "rollout_epilogue must be 0 or 1");
+            sim->rollout_epilogue = (int)value;
             return PCC_OK;
         case PCC_TUNE_NOISE_SORTED:
             if (value != 0.0 && value != 1.0 && value != 2.0) return fail(PCC_EINVAL, "noise_sorted must be 0, 1 or 2");
@@ -1179,6 +1189,126 @@ int pcc_step_many(pcc_sim_t *sim, const void *actions, int actions_f64, int n_st
             snprintf(why, sizeof why, "%s", g_err);
             return fail(rc, "pcc_step_many stopped after %d of %d steps: %s", t, n_steps, why);
         }
+    }
+    return PCC_OK;
+}
+
+namespace {
+// Whether after_mi will enqueue reset launches after the coming step (they rewrite observation rows after its retire launch): at
+// the episode boundary of a batch in lockstep, or out of lockstep when finished envs are not restarted inside the step.
+bool reset_follows(const pcc_sim_t *sim, int auto_reset) {
+    if (!auto_reset) return false;
+    const bool may_be_done = !sim->lockstep || sim->host_steps + 1u >= sim->d.max_steps;
+    return may_be_done && !restarts_in_step(sim, auto_reset);
+}
+}  // namespace
+
+int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps, const float *noise, float *obs_io, float *act_out,
+                float *logp_out, float *value_out, float *reward_out, uint8_t *done_out, double *steps_out, int auto_reset,
+                void *stream) {
+    if (!sim || !params || !obs_io || n_steps < 1) return fail(PCC_EINVAL, "pcc_rollout: NULL sim, params or obs_io, or n_steps < 1");
+    if (sim->d.use_cwnd)
+        return fail(PCC_EINVAL, "pcc_rollout: the congestion-window mode takes two actions per sender; the policy gives one");
+    if (!sim->ever_reset) return fail(PCC_ESTATE, "pcc_rollout before pcc_reset (the reference raises TypeError: run_dur is None)");
+    if (sim->send_pending) return fail(PCC_ESTATE, "pcc_rollout between pcc_step_send and pcc_step_retire");
+    DeviceGuard guard(sim->device);
+    const Dev &d = sim->d;
+    const int D = d.HF;
+    const size_t row = (size_t)d.n * d.ns;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    float *act = act_out;
+    if (!act) {   // the caller keeps no actions: two rows, step t's in row t % 2
+        if (sim->roll_act_floats < 2 * row) {
+            if (sim->roll_act) (void)hipFree(sim->roll_act);
+            sim->roll_act = nullptr;
+            sim->roll_act_floats = 0;
+            if (hipMalloc(&sim->roll_act, 2 * row * sizeof(float)) != hipSuccess)
+                return fail(PCC_ENOMEM, "pcc_rollout: hipMalloc of the action rows failed");
+            sim->roll_act_floats = 2 * row;
+        }
+        act = sim->roll_act;
+    }
+    const int act_rows = act_out ? 0 : 2;
+    auto act_at = [&](int t) { return act + (size_t)(act_rows ? t % act_rows : t) * row; };
+    auto obs_at = [&](int t) { return obs_io + (size_t)t * row * D; };
+    auto rew_at = [&](int t) { return reward_out ? reward_out + (size_t)t * row : nullptr; };
+    auto done_at = [&](int t) { return done_out ? done_out + (size_t)t * d.n : nullptr; };
+    auto steps_at = [&](int t) { return steps_out ? steps_out + (size_t)t * row * PCC_STEP_COLS : nullptr; };
+    // the policy on observation row t, as one stand-alone launch (pcc_policy_act)
+    auto policy = [&](int t) -> int {
+        const int rc = pcc_policy_act(obs_at(t), (int64_t)row, D, params, h1, h2, noise ? noise + (size_t)t * row : nullptr, nullptr,
+                                      act_at(t), logp_out ? logp_out + (size_t)t * row : nullptr,
+                                      value_out ? value_out + (size_t)t * row : nullptr, stream);
+        if (rc == -2) return fail(PCC_EINVAL, "pcc_policy_act has no kernel for observation length %d with hidden sizes (%d, %d)", D, h1, h2);
+        if (rc == -1) return fail(PCC_EINVAL, "pcc_policy_act refuses hidden sizes (%d, %d) at observation length %d", h1, h2, D);
+        if (rc != 0) return fail(PCC_EHIP, "policy kernel launch: %s", hipGetErrorString(hipGetLastError()));
+        return PCC_OK;
+    };
+    auto stopped = [&](int rc, int t) -> int {
+        char why[400];
+        snprintf(why, sizeof why, "%s", g_err);
+        return fail(rc, "pcc_rollout stopped after %d of %d steps: %s", t, n_steps, why);
+    };
+    // The policy inside the env's launches: the reference's --arch 32,16 at an observation length the stand-alone kernel has
+    // an instantiation for (the epilogue gives its bits), one sender, the send + retire launches (no event loop, no one-launch step)
+    const bool fixed_net = h1 == kPolH1 && h2 == kPolH2 && (D == 3 || D == 6 || D == 12 || D == 30 || D == 36 || D == 60);
+    const bool in_step = fixed_net && d.ns == 1 && !d.engine;
+    PolicyArgs pa{params, pol_params(D), D, act_rows, 0, noise, act, logp_out, value_out};
+    if (in_step && d.n >= (int64_t)sim->list_min_envs && !sim->fused && sim->rollout_epilogue) {
+        // Epilogue path (PCC_TUNE_ROLLOUT_EPILOGUE; off by default: measured slower than the launches it replaces):
+        // the retire launch of step t computes the action of step t + 1 -- unless reset launches follow the step (they rewrite
+        // observation rows after it): then a stand-alone policy launch behind them.  Step 0 has one too; the last step of the
+        // call runs plain.
+        bool need = true;
+        for (int t = 0; t < n_steps; t++) {
+            int rc = need ? policy(t) : PCC_OK;
+            const bool epi = t + 1 < n_steps && !reset_follows(sim, auto_reset);
+            if (rc == PCC_OK) {
+                next_step_seq(sim, st);
+                const int restart = restart_mode(sim, auto_reset);
+                rc = launch_send(sim, 0, 0, 0, act_at(t), 0, st);
+                pa.t0 = t;
+                if (rc == PCC_OK)
+                    rc = launch_retire_half(sim, 0, 0, 0, 0, restart, obs_at(t + 1), rew_at(t), done_at(t), steps_at(t), st,
+                                            epi ? &pa : nullptr);
+                if (rc == PCC_OK && (restart & 2)) queue_refill(sim, st);
+                if (rc == PCC_OK) rc = after_mi(sim, obs_at(t + 1), auto_reset, st);
+            }
+            if (rc != PCC_OK) return stopped(rc, t);
+            need = !epi;
+        }
+        return PCC_OK;
+    }
+    if (in_step && d.n < (int64_t)sim->list_min_envs && (sim->lockstep || !auto_reset)) {
+        // Small-batch loop path: the steps up to the next episode boundary are ONE launch of step_small_policy_kernel (as in
+        // pcc_step_many), the policy in its loop; the first action of every segment from a stand-alone policy launch
+        int t = 0;
+        while (t < n_steps) {
+            int seg = n_steps - t;
+            if (sim->lockstep && auto_reset) {
+                const int left = (int)d.max_steps - (int)sim->host_steps;
+                if (seg > (left > 1 ? left : 1)) seg = left > 1 ? left : 1;
+            }
+            int rc = policy(t);
+            if (rc == PCC_OK) {
+                next_step_seq(sim, st);
+                pa.t0 = t;
+                launch_step_small(d, d.rng_mode == PCC_RNG_TRACE, st, nullptr, 0, obs_at(t + 1), rew_at(t), done_at(t), steps_at(t), seg, 0,
+                                  &pa);
+                rc = check_hip(hipGetLastError(), "step kernel launch");
+                sim->host_steps += (uint32_t)(seg - 1);
+                if (rc == PCC_OK) rc = after_mi(sim, obs_at(t + seg), auto_reset, st);
+            }
+            if (rc != PCC_OK) return stopped(rc, t);
+            t += seg;
+        }
+        return PCC_OK;
+    }
+    // Launch by launch: the contract's loop as it reads
+    for (int t = 0; t < n_steps; t++) {
+        int rc = policy(t);
+        if (rc == PCC_OK) rc = pcc_step(sim, act_at(t), 0, obs_at(t + 1), rew_at(t), done_at(t), steps_at(t), auto_reset, stream);
+        if (rc != PCC_OK) return stopped(rc, t);
     }
     return PCC_OK;
 }

@@ -65,6 +65,59 @@ __global__ __launch_bounds__(4 * kWave, PCC_SMALL_OCC) void step_small_kernel(De
     }
 }
 
+// step_small_kernel<1, TRACE> with the policy in the loop (pcc_rollout): after the retire part of step t (but the last) each env's
+// group computes the env's action of step t + 1 from the observation row it has just written (pcc_policy_dev.h) into the act
+// rows the send part of step t + 1 reads -- behind the workgroup barrier between the steps.  The parameter block sits in LDS
+// once per launch (the workgroup runs every step of the segment).  A kernel of its own rather than a template switch of
+// step_small_kernel: that one's code stays exactly what it was.
+__device__ __forceinline__ float *small_pol_lds() {
+    extern __shared__ float s_pol_dyn[];
+    return s_pol_dyn;
+}
+
+template <bool TRACE>
+__global__ __launch_bounds__(4 * kWave, PCC_SMALL_OCC) void step_small_policy_kernel(Dev D, float *obs_out, float *reward_out,
+                                                                                  uint8_t *done_out, double *steps_out, int n_steps,
+                                                                                  PolicyArgs pol) {
+    const uint32_t lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
+    const int64_t base = (int64_t)blockIdx.x * kSmallEnvs;
+    __shared__ EnvSlot<1> s_slots[kSlots];
+    float *w = small_pol_lds() + kSmallEnvs * kPolScratch;
+    for (int k = (int)threadIdx.x; k < pol.n_params; k += 4 * kWave) w[k] = pol.params[k];
+    __syncthreads();
+#pragma unroll 1
+    for (int t = 0; t < n_steps; t++) {
+        const float *act_t = pol.act + pol_act_row(pol, pol.t0 + t) * D.n;
+        if (wv == 0) {
+            const int64_t i = base + lane;
+            const bool has = lane < (uint32_t)kSmallEnvs && i < D.n;
+            uint32_t pk = 0;
+            const uint64_t left = send_light_item<1, TRACE>(D, lane, has ? i : 0, has, blockIdx.x, 0, 0, act_t, 0, pk);
+            if (left) {
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+                (void)send_wave_item<1, TRACE, 1>(D, lane, has ? i : 0, ((left >> lane) & 1ull) != 0ull, false, 0xFFFFFFFFu, 0, 0, act_t, 0, s_slots);
+            }
+        }
+        __syncthreads();
+        float *obs_t = obs_out + (int64_t)t * D.n * D.HF;
+        float *rew_t = reward_out ? reward_out + (int64_t)t * D.n : nullptr;
+        uint8_t *done_t = done_out ? done_out + (int64_t)t * D.n : nullptr;
+        double *steps_t = steps_out ? steps_out + (int64_t)t * D.n * PCC_STEP_COLS : nullptr;
+        {
+            const int64_t i = base + (int64_t)(wv * 8u + lane / 8u);
+            Group g;
+            g.lane = lane & 7u;
+            g.shift = lane & ~7u;
+            if (i < base + kSmallEnvs && i < D.n) {
+                (void)retire_env<1, false, 8>(D, i, g, 0, 0, 0, 0, obs_t, rew_t, done_t, steps_t, nullptr, 0);
+                if (t + 1 < n_steps)
+                    policy_group<8>(pol, w, small_pol_lds() + (i - base) * kPolScratch, obs_t + i * D.HF, i, D.n, g.lane, pol.t0 + t + 1);
+            }
+        }
+        if (t + 1 < n_steps) __syncthreads();  // the next step's send part reads the actions and the state this step wrote
+    }
+}
+
 // ======================================================================================
 // reset_init_kernel: ns:454-477 -- parameters, fresh link/sender/history state.  The two warm-up
 // MIs (ns:478-479) are run by send_kernel / retire_kernel in warm mode on the marked envs.
@@ -120,8 +173,15 @@ __global__ void forget_ring_slots_kernel(Dev D) {
 namespace pcc {
 
 void launch_step_small(const Dev &d, bool trace, hipStream_t st, const void *actions, int actions_f64, float *obs_out,
-                       float *reward_out, uint8_t *done_out, double *steps_out, int n_steps, int64_t act_stride) {
+                       float *reward_out, uint8_t *done_out, double *steps_out, int n_steps, int64_t act_stride,
+                       const PolicyArgs *pol) {
     const dim3 grid((unsigned)((d.n + kSmallEnvs - 1) / kSmallEnvs)), block(4 * kWave);
+    if (pol) {   // (one sender: the host asks for nothing else)
+        const size_t lds = (size_t)(kSmallEnvs * kPolScratch + pol->n_params) * sizeof(float);
+        if (trace) hipLaunchKernelGGL(step_small_policy_kernel<true>, grid, block, lds, st, d, obs_out, reward_out, done_out, steps_out, n_steps, *pol);
+        else hipLaunchKernelGGL(step_small_policy_kernel<false>, grid, block, lds, st, d, obs_out, reward_out, done_out, steps_out, n_steps, *pol);
+        return;
+    }
 #define PCC_S(NS_, TR_) \
     hipLaunchKernelGGL((step_small_kernel<NS_, TR_>), grid, block, 0, st, d, actions, actions_f64, obs_out, reward_out, done_out, steps_out, n_steps, act_stride)
     if (d.ns == 1) { if (trace) PCC_S(1, true); else PCC_S(1, false); }

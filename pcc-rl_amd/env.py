@@ -313,6 +313,35 @@ class BatchedNetworkEnv(object):
                                     _ptr(done_out), _ptr(steps_out), 1 if self.auto_reset else 0, self._stream()))
         self._t += T
 
+    def rollout(self, params, noise, obs_b, act_b, logp_b, val_b, rew_b, done_b, steps_b=None, arch=(32, 16)):
+        """T closed-loop steps in ONE library call (pcc_rollout): step t's action is the policy's (pcc_policy_act's parameter
+        block ``params``, hidden sizes ``arch``) on observation row t, with standard-normal draws ``noise`` [T, N(, S)] (None:
+        deterministic, the mean).  obs_b [T+1, N(, S), H*F]: row 0 is read, rows 1..T are written; act_b [T, N(, S)(, 1)], logp_b /
+        val_b / rew_b [T, N(, S)], done_b [T, N], steps_b [T, N, S, 19] float64 -- every output but obs_b may be None, all contiguous
+        on the env's device.  Bit-identical to T rounds of the policy kernel and step_into(); with one sender and the reference's
+        32,16 policy a small batch runs the policy inside the env's launches.  If the call fails part-way the error says after how many steps;
+        the env's step counter is not advanced then (reset before going on)."""
+        if params is None or obs_b is None:
+            raise ValueError("rollout: params and obs_b are required")
+        T = int(obs_b.shape[0]) - 1
+        if T < 1:
+            raise ValueError("rollout: obs_b needs T + 1 >= 2 rows")
+        if len(arch) != 2:
+            raise ValueError("rollout: arch must be two hidden sizes")
+        N, S, D = self.n_envs, self.n_senders, self.obs_dim
+        for t, n, dt in ((obs_b, (T + 1) * N * S * D, (torch.float32,)), (params, None, (torch.float32,)),
+                         (noise, T * N * S, (torch.float32,)), (act_b, T * N * S, (torch.float32,)),
+                         (logp_b, T * N * S, (torch.float32,)), (val_b, T * N * S, (torch.float32,)),
+                         (rew_b, T * N * S, (torch.float32,)), (done_b, T * N, (torch.uint8, torch.bool)),
+                         (steps_b, T * N * S * native.PCC_STEP_COLS, (torch.float64,))):
+            if t is not None and ((n is not None and t.numel() != n) or t.dtype not in dt or not t.is_contiguous()
+                                  or t.device != self.device):
+                raise ValueError("rollout: a tensor has the wrong size, dtype, layout or device")
+        check(self._L.pcc_rollout(self._h, _ptr(params), int(arch[0]), int(arch[1]), T, _ptr(noise), _ptr(obs_b), _ptr(act_b),
+                                  _ptr(logp_b), _ptr(val_b), _ptr(rew_b), _ptr(done_b), _ptr(steps_b),
+                                  1 if self.auto_reset else 0, self._stream()))
+        self._t += T
+
     # ------------------------------------------------------------------ introspection
     def state(self, name):
         """Copy of one internal state field as a tensor (see native.FIELDS)."""

@@ -22,12 +22,29 @@ import torch
 from torch import nn
 
 
+class AlignedLinear(nn.Linear):
+    """nn.Linear whose forward reads weight and bias from 64-byte aligned memory.  After MlpPolicy.share_flat() the parameters
+    are views into ONE flat block at the offsets of the packed layout, and the CPU BLAS result for an operand at another
+    alignment can differ in the last bits (the 16-wide output layer of vf, 8 bytes off a 16-byte boundary, on AMD EPYC): a
+    misaligned parameter is read through an aligned copy, so moving the parameters never changes what the policy computes.
+    (On the GPU the forward is nn.Linear's as it was.)"""
+
+    def forward(self, x):
+        w, b = self.weight, self.bias
+        if not torch.jit.is_scripting() and w.device.type == "cpu":
+            if w.data_ptr() % 64:
+                w = w.clone()
+            if b is not None and b.data_ptr() % 64:
+                b = b.clone()
+        return nn.functional.linear(x, w, b)
+
+
 def mlp(inp, hidden, out):
     layers, last = [], inp
     for h in hidden:
-        layers += [nn.Linear(last, h), nn.Tanh()]
+        layers += [AlignedLinear(last, h), nn.Tanh()]
         last = h
-    layers.append(nn.Linear(last, out))
+    layers.append(AlignedLinear(last, out))
     return nn.Sequential(*layers)
 
 
@@ -176,10 +193,16 @@ def ppo_loss(policy, obs, act, logp_old, adv, ret, clip=0.2, ent_coef=0.01):
 
 class PPO(object):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
-                 epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True):
+                 epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
-        optimiser steps per epoch, thousands of launches of a few microseconds of work each."""
+        optimiser steps per epoch, thousands of launches of a few microseconds of work each.
+        policy_in_step: collect() runs the horizon as ONE closed-loop library call per env (group) -- env.rollout, pcc_rollout:
+        the policy inside the env's own launches -- with the same numbers, bit for bit, as the policy kernel + step_into loop."""
+        if policy_in_step and torch.device(env.device).type != "cuda":
+            raise ValueError("PPO(policy_in_step=True) runs the policy inside the env's HIP launches: it needs the env on the GPU "
+                             "(device=%r)" % (env.device,))
+        self.policy_in_step = bool(policy_in_step)
         self.env, self.gamma, self.lam, self.clip, self.ent_coef = env, gamma, lam, clip, ent_coef
         self.epochs, self.minibatch, self.horizon = epochs, minibatch, horizon
         torch.manual_seed(seed)
@@ -228,7 +251,39 @@ class PPO(object):
         obs_b[0] = self.obs
         fused = self.policy.fused_ok(obs_b[0]) and env.n_senders == 1
         groups = getattr(env, "groups", None)
-        if fused and groups is not None:
+        if self.policy_in_step and not fused:
+            raise ValueError("PPO(policy_in_step=True) needs the fused rollout: a two-hidden-layer policy, one sender, on the GPU")
+        if self.policy_in_step:
+            # the whole horizon as one pcc_rollout per env (group): the same noise, parameters and rows as the loop below
+            arch = tuple(m.out_features for m in self.policy.pi if isinstance(m, nn.Linear))[:2]
+            params = self.policy.flat_params()
+            noise = torch.randn((T, N), device=dev)
+            u8 = done_b.view(torch.uint8)
+            if groups is None:
+                env.rollout(params, noise, obs_b, act_b, logp_b, val_b, rew_b, u8, arch=arch)
+            else:
+                n = env.group_size
+                cur = torch.cuda.current_stream(dev)
+                # (a group's rows of [T(+1), N] buffers are strided: each group fills contiguous buffers of its own on its stream)
+                parts = []
+                for g, eg in enumerate(groups):
+                    lo, hi = g * n, (g + 1) * n
+                    env.streams[g].wait_stream(cur)
+                    with torch.cuda.stream(env.streams[g]):
+                        ob = torch.empty((T + 1, n, env.obs_dim), device=dev)
+                        ob[0] = obs_b[0, lo:hi]
+                        bufs = (torch.empty((T, n, 1), device=dev), torch.empty((T, n), device=dev), torch.empty((T, n), device=dev),
+                                torch.empty((T, n), device=dev), torch.empty((T, n), dtype=torch.uint8, device=dev))
+                        eg.rollout(params, noise[:, lo:hi].contiguous(), ob, *bufs, arch=arch)
+                        parts.append((lo, hi, ob, bufs))
+                for g, (lo, hi, ob, bufs) in enumerate(parts):
+                    cur.wait_stream(env.streams[g])
+                    obs_b[1:, lo:hi] = ob[1:]
+                    for dst, src in zip((act_b, logp_b, val_b, rew_b, u8), bufs):
+                        dst[:, lo:hi] = src
+                    for tns in (ob,) + bufs:
+                        tns.record_stream(cur)
+        elif fused and groups is not None:
             # Double-buffered sampling (GroupedNetworkEnv: the same envs as G groups on their own streams): group g's
             # policy kernel and env step are queued on stream g, nothing joins the groups inside the rollout -- while one
             # group's env launches run out their tails (a third of the wavefront slots busy), the

@@ -23,8 +23,10 @@ extern "C" {
  * noise     [n_envs] standard-normal draws, device; NULL = deterministic (act = mean, logp of the mean)
  * mean_out, act_out, logp_out, value_out   [n_envs] each, device; any may be NULL
  * stream    HIP stream; nothing synchronizes
- * Returns 0; -1 bad arguments / too many parameters for LDS; -2 no kernel instantiated for this obs_dim
- * (30, 36, 3, 6, 12, 60 are: the caller falls back to its framework path); -3 launch failure.
+ * Returns 0 for every shape of the domain of pcc_ppo_supported (1 <= obs_dim <= 128, 1 <= h1, h2 <= 64: obs_dim, h1 and h2
+ * are run-time values; --arch 32,16 at 30, 36, 3, 6, 12 or 60 observations runs a fully unrolled kernel); -1 bad arguments
+ * (NULL obs / params, n_envs < 1, a hidden size outside 1 .. 64); -2 obs_dim outside 1 .. 128 (the caller falls back to its
+ * framework path); -3 launch failure.
  */
 int pcc_policy_act(const float *obs, int64_t n_envs, int obs_dim, const float *params, int h1, int h2,
                    const float *noise, float *mean_out, float *act_out, float *logp_out, float *value_out,
@@ -44,9 +46,13 @@ int pcc_policy_act(const float *obs, int64_t n_envs, int obs_dim, const float *p
  * grad_out  [n_params] or NULL: the gradient that was applied
  * stats_out [4] or NULL: {mean clipped surrogate (= -policy loss), mean squared value error (= 2 x value loss),
  *           fraction of samples with |r - 1| > clip, 0}
- * Returns 0; -1 bad arguments; -2 no kernel for this shape (h1, h2 = 32, 16 and obs_dim 30, 12, 6, 3 are built: the caller
- * falls back to its framework path); -3 launch failure.
+ * Returns 0; -1 bad arguments; -2 no kernel for this shape: one outside the domain of pcc_ppo_supported (the caller falls
+ * back to its framework path); -3 launch failure.
+ *
+ * pcc_ppo_supported: 1 if both pcc_policy_act and pcc_ppo_minibatch_step have a kernel for a policy of two tanh hidden layers
+ * h1, h2 on obs_dim observations (1 <= obs_dim <= 128, 1 <= h1, h2 <= 64), else 0.  Host only: needs no GPU.
  */
+int pcc_ppo_supported(int obs_dim, int h1, int h2);
 int pcc_ppo_scratch_floats(int obs_dim, int h1, int h2);
 int pcc_ppo_minibatch_step(const float *obs, const float *act, const float *logp_old, const float *adv, const float *ret,
                            const int64_t *perm, int64_t start, int64_t count, int obs_dim, int h1, int h2, float *params,

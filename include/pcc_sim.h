@@ -356,13 +356,16 @@ int pcc_step_many(pcc_sim_t *sim, const void *actions, int actions_f64, int n_st
  *   obs_io      [n_steps+1][N][S][H*F]: row 0 is read (the current observation), rows 1..n_steps are written
  *   noise       [n_steps][N][S] standard-normal draws; NULL = deterministic (act = the mean)
  *   act_out, logp_out, value_out  [n_steps][N][S]; reward_out, done_out, steps_out: pcc_step_many's shapes
- * Every output but obs_io may be NULL (act_out NULL: the handle keeps the actions in two rows of its own).  With one sender and
- * the reference's --arch 32,16 at an observation length pcc_policy_act has a kernel for, a small batch runs the policy inside
+ * Every output but obs_io may be NULL (act_out NULL: the handle keeps the actions in two rows of its own).  Any policy of
+ * pcc_policy_act's domain works (up to 128 observations, hidden layers up to 64 wide: pcc_ppo_supported) -- except that the
+ * reference's --arch 32,16 keeps the rollout domain it had: 3, 6, 12, 30, 36 or 60 observations, PCC_EINVAL at another length
+ * (the loop below works there; only this call refuses).  With one sender and --arch 32,16, a small batch runs the policy inside
  * the loop of the one-launch segments of pcc_step_many; at full size the policy goes into the epilogue of the retire launch
  * when PCC_TUNE_ROLLOUT_EPILOGUE asks for it (measured slower: off by default, the steps launch by launch).  Other
- * configurations (two senders, the event-loop build, other sizes, the one-launch step PCC_TUNE_FUSED) run the loop above as it
- * reads.  PCC_EINVAL: the congestion-window mode (two actions per sender), NULL params / obs_io, n_steps < 1, a policy shape
- * pcc_policy_act has no kernel for; PCC_ESTATE: what pcc_step refuses.  On an error the message says after how many steps the
+ * configurations (two senders, the event-loop build, other policy shapes, the one-launch step PCC_TUNE_FUSED) run the loop above
+ * as it reads.  PCC_EINVAL: the congestion-window mode (two actions per sender), NULL params / obs_io, n_steps < 1, a policy shape
+ * outside pcc_policy_act's domain (more than 128 observations, a hidden layer wider than 64) or --arch 32,16 at an observation
+ * length other than the six above; PCC_ESTATE: what pcc_step refuses.  On an error the message says after how many steps the
  * call stopped.  No reference counterpart (the reference's agent calls step() once per interval). */
 int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps, const float *noise, float *obs_io,
                 float *act_out, float *logp_out, float *value_out, float *reward_out, uint8_t *done_out, double *steps_out,

@@ -5,10 +5,15 @@
 // not starved by a dozen small framework launches per step.  One lane per env; the few thousand
 // parameters sit in LDS, every lane walks them in the same order (broadcast reads, no bank conflicts);
 // fp32 like the framework path it replaces.  No MFMA: 65 536 x ~3 kFLOP is microseconds of plain FMAs.
+// That holds for the kernels of this file (the reference's --arch 32,16 fully unrolled at six observation lengths, and the
+// older generic kernel at those lengths below 8 192 parameters).  Every other shape of the supported domain (up to 128
+// observations, hidden layers up to 64 wide, run-time sizes) takes policy_act_tiled_kernel (pcc_mlp_tiles.h): the gradient
+// kernel's MFMA forward, weights and activations in LDS, no private arrays.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "pcc_mlp_tiles.h"
 #include "pcc_policy.h"
 #include "pcc_policy_dev.h"
 
@@ -130,7 +135,11 @@ extern "C" int pcc_policy_act(const float *obs, int64_t n_envs, int obs_dim, con
     if (h1 < 1 || h2 < 1 || h1 > kMaxHidden || h2 > kMaxHidden) return -1;
     const int n_net = h1 * obs_dim + h1 + h2 * h1 + h2 + h2 + 1;
     const int n_params = 2 * n_net + 1;
-    if (n_params > kMaxParams) return -1;
+    const bool old_length = obs_dim == 30 || obs_dim == 36 || obs_dim == 3 || obs_dim == 6 || obs_dim == 12 || obs_dim == 60;
+    if (n_params > kMaxParams || !old_length) {   // what the kernels of this file refuse: the tiled kernel (-2 outside its domain)
+        const pcc_tiles::ActArgs a{obs, n_envs, obs_dim, h1, h2, params, noise, mean_out, act_out, logp_out, value_out};
+        return pcc_tiles::launch_act(a, static_cast<hipStream_t>(stream));
+    }
     const dim3 grid((unsigned)((n_envs + 255) / 256)), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (h1 == 32 && h2 == 16) {   // the reference's --arch: the fully unrolled build
@@ -163,7 +172,7 @@ extern "C" int pcc_policy_act(const float *obs, int64_t n_envs, int obs_dim, con
         PCC_POLICY_CASE(12)
         PCC_POLICY_CASE(60)
 #undef PCC_POLICY_CASE
-        default: return -2;   // observation length without an instantiation: the caller falls back to the framework path
+        default: return -2;   // (not reached: the lengths above)
     }
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -16,12 +16,17 @@
 //   ppo_adam_kernel   sums the partial gradients in a fixed order (deterministic), adds the entropy
 //                     term, applies Adam (torch.optim.Adam's arithmetic), writes the parameters in place.
 //
+// ppo_grad_mfma_kernel is built for --arch 32,16 at 30, 12, 6 and 3 observations; every other shape of the supported domain
+// (pcc_ppo_supported: up to 128 observations, hidden layers up to 64 wide) takes ppo_grad_tiled_kernel (pcc_mlp_tiles.h), the
+// tiled generalisation with run-time sizes, which writes partial gradients of the same layout for the same ppo_adam_kernel.
+//
 // Plus the GAE recursion as one launch (thread = env, T steps backwards).  fp32 like the framework path; checked against
 // torch autograd in tests/test_ppo.py.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
+#include "pcc_mlp_tiles.h"
 #include "pcc_policy.h"
 
 namespace {
@@ -410,9 +415,17 @@ __global__ void gae_kernel(const float *__restrict__ rew, const float *__restric
 
 }  // namespace
 
+// the shapes ppo_grad_mfma_kernel is instantiated for; the rest of the domain goes to the tiled kernel
+static bool mfma_fixed_shape(int obs_dim, int h1, int h2) {
+    return h1 == 32 && h2 == 16 && (obs_dim == 30 || obs_dim == 3 || obs_dim == 6 || obs_dim == 12);
+}
+
+extern "C" int pcc_ppo_supported(int obs_dim, int h1, int h2) { return pcc_tiles::in_domain(obs_dim, h1, h2) ? 1 : 0; }
+
 extern "C" int pcc_ppo_scratch_floats(int obs_dim, int h1, int h2) {
     const int n_net = h1 * obs_dim + h1 + h2 * h1 + h2 + h2 + 1;
-    return kMaxBlocks * (2 * n_net + 1 + 4);
+    const int blocks = mfma_fixed_shape(obs_dim, h1, h2) || !pcc_tiles::in_domain(obs_dim, h1, h2) ? kMaxBlocks : pcc_tiles::kMaxGradBlocks;
+    return blocks * (2 * n_net + 1 + 4);
 }
 
 extern "C" int pcc_ppo_minibatch_step(const float *obs, const float *act, const float *logp_old, const float *adv,
@@ -422,26 +435,34 @@ extern "C" int pcc_ppo_minibatch_step(const float *obs, const float *act, const 
                                       float *grad_out, float *stats_out, void *stream) {
     if (!obs || !act || !logp_old || !adv || !ret || !params || !scratch || count < 1 || start < 0) return -1;
     if (lr != 0.0f && (!adam_m || !adam_v || adam_step < 1)) return -1;
-    if (h1 != 32 || h2 != 16) return -2;
     const int n_net = h1 * obs_dim + h1 + h2 * h1 + h2 + h2 + 1;
     const int n_params = 2 * n_net + 1;
-    const int64_t tiles = (count + kWave - 1) / kWave;
-    int64_t blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-    if (blocks > kMaxBlocks) blocks = kMaxBlocks;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)blocks), block(kWavesPerBlock * kWave);
-    switch (obs_dim) {
+    int64_t blocks;
+    if (mfma_fixed_shape(obs_dim, h1, h2)) {
+        const int64_t tiles = (count + kWave - 1) / kWave;
+        blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+        if (blocks > kMaxBlocks) blocks = kMaxBlocks;
+        const dim3 grid((unsigned)blocks), block(kWavesPerBlock * kWave);
+        switch (obs_dim) {
 #define PCC_PPO_CASE(DD)                                                                                                   \
     case DD:                                                                                                               \
         hipLaunchKernelGGL((ppo_grad_mfma_kernel<DD, 32, 16>), grid, block, 0, st, obs, act, logp_old, adv, ret, perm, start, \
                            count, params, clip, scratch);                                                                 \
         break;
-        PCC_PPO_CASE(30)   // history 10 x 3 features: the reference's default observation (ns:382-388)
-        PCC_PPO_CASE(3)
-        PCC_PPO_CASE(6)
-        PCC_PPO_CASE(12)
+            PCC_PPO_CASE(30)   // history 10 x 3 features: the reference's default observation (ns:382-388)
+            PCC_PPO_CASE(3)
+            PCC_PPO_CASE(6)
+            PCC_PPO_CASE(12)
 #undef PCC_PPO_CASE
-        default: return -2;   // the caller falls back to its framework path
+            default: return -2;
+        }
+    } else {   // any other shape of the domain: the tiled kernel (-2 outside: the caller falls back to its framework path)
+        const pcc_tiles::GradArgs a{obs, act, logp_old, adv, ret, perm, start, count, obs_dim, h1, h2, params, clip, scratch};
+        int nb = 0;
+        const int rc = pcc_tiles::launch_grad(a, st, &nb);
+        if (rc != 0) return rc;
+        blocks = nb;
     }
     if (hipGetLastError() != hipSuccess) return -3;
     const float bias1 = lr != 0.0f ? 1.0f - powf(beta1, (float)adam_step) : 1.0f;

@@ -12,7 +12,8 @@ image, so there is nothing to check agent-level parity against (SURVEY.md sectio
 checked (tests/test_ppo.py): the GAE recursion and the clipped objective against plain loops (CPU
 tests); on the GPU the HIP kernels of the fused path -- policy forward (pcc_policy.hip), the
 fp32-MFMA gradient kernel and the Adam step (pcc_ppo.hip: pcc_ppo_minibatch_step), the GAE kernel
--- against float64 autograd, torch.optim.Adam and the loop; that a short run on the GPU improves
+-- against float64 autograd, torch.optim.Adam and the loop, for the reference's shape and (tests/test_ppo_shapes.py) for other
+--arch and observation lengths of the library's domain (pcc_ppo_supported: csrc/pcc_mlp_tiles.h); that a short run on the GPU improves
 the return; and what the whole loop costs next to the env alone (tools/ppo_throughput.py,
 profiles/r04_v2_ppo_throughput.json).
 """
@@ -134,7 +135,7 @@ class MlpPolicy(nn.Module):
         rc = lib().pcc_policy_act(ptr(obs.contiguous()), n, D, ptr(params), linears[0].out_features, linears[1].out_features,
                                   ptr(noise if stochastic else None), None, ptr(a), ptr(logp), ptr(v),
                                   ctypes.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream))
-        if rc != 0:   # e.g. an observation length without a kernel instantiation
+        if rc != 0:   # a shape outside the library's domain (include/pcc_policy.h: pcc_ppo_supported)
             _warn_once("pcc_policy_act has no kernel for %d observations x hidden %d-%d: the policy forward runs on the framework "
                        "path (several times slower)" % (D, linears[0].out_features, linears[1].out_features))
             a2, logp2, v2 = self.act(obs, stochastic)
@@ -233,8 +234,10 @@ class PPO(object):
     def _fused_update_ok(self):
         env = self.env
         arch = [m.out_features for m in self.policy.pi if isinstance(m, nn.Linear)]
-        return (torch.device(env.device).type == "cuda" and arch == [32, 16, 1] and env.obs_dim in (30, 12, 6, 3)
-                and env.n_senders == 1)
+        if not (torch.device(env.device).type == "cuda" and len(arch) == 3 and arch[2] == 1 and env.n_senders == 1):
+            return False
+        from .native import lib
+        return lib().pcc_ppo_supported(int(env.obs_dim), arch[0], arch[1]) == 1
 
     def collect(self):
         """One rollout of `horizon` steps of every env.  The policy kernel reads the observation row the env wrote and
@@ -360,8 +363,9 @@ class PPO(object):
             self.adam_t += 1
         ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         D = obs_f.shape[1]
+        h1, h2 = [m.out_features for m in self.policy.pi if isinstance(m, nn.Linear)][:2]
         rc = lib().pcc_ppo_minibatch_step(ptr(obs_f), ptr(act_f), ptr(logp_f), ptr(adv_f), ptr(ret_f), ptr(perm), start, count,
-                                          D, 32, 16, ptr(self.flat), ptr(self.adam_m), ptr(self.adam_v), max(self.adam_t, 1),
+                                          D, h1, h2, ptr(self.flat), ptr(self.adam_m), ptr(self.adam_v), max(self.adam_t, 1),
                                           lr, 0.9, 0.999, self.adam_eps, self.clip, self.ent_coef, ptr(self.scratch),
                                           ptr(grad_out), ptr(self.stats_buf),
                                           ctypes.c_void_p(torch.cuda.current_stream(obs_f.device).cuda_stream))

@@ -1,19 +1,34 @@
 #!/usr/bin/env python3
 """What the whole training loop costs next to the env alone (GPU box only):
 env-steps/s of (a) the env stepped with pre-generated actions, (b) the PPO rollout (policy forward +
-sampling + env step + buffers), (c) rollout + GAE + the PPO epochs, all at the bench size."""
-import json, os, sys, time
+sampling + env step + buffers), (c) rollout + GAE + the PPO epochs, all at the bench size.
+   python tools/ppo_throughput.py [n_envs [horizon]] [--arch 64,32] [--history 3] [--features all | name,name,...]
+(defaults: the reference's policy 32,16 on history 10 x the 3 default features; the per-shape comparison of the fused and the
+framework paths is tools/ppo_shapes.py)"""
+import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import pcc_rl_amd
 from pcc_rl_amd.ppo import PPO
 
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
-T = int(sys.argv[2]) if len(sys.argv) > 2 else 64
+ap = argparse.ArgumentParser()
+ap.add_argument("n_envs", nargs="?", type=int, default=65536)
+ap.add_argument("horizon", nargs="?", type=int, default=64)
+ap.add_argument("--arch", default="32,16")
+ap.add_argument("--history", type=int, default=None)
+ap.add_argument("--features", default=None)
+args = ap.parse_args()
+N, T = args.n_envs, args.horizon
+ARCH = tuple(int(x) for x in args.arch.split(","))
+ENV_KW = {}
+if args.history is not None:
+    ENV_KW["history_len"] = args.history
+if args.features is not None:
+    ENV_KW["features"] = list(pcc_rl_amd.METRIC_NAMES) if args.features == "all" else args.features.split(",")
 dev = torch.device("cuda:0")
-env = pcc_rl_amd.BatchedNetworkEnv(N, device=dev, seed=0)
+env = pcc_rl_amd.BatchedNetworkEnv(N, device=dev, seed=0, **ENV_KW)
 # the reference's ratio: 8192 samples per iteration in minibatches of 2048 = 4 minibatches per epoch
-agent = PPO(env, horizon=T, seed=0, minibatch=max(2048, N * T // 4))
+agent = PPO(env, arch=ARCH, horizon=T, seed=0, minibatch=max(2048, N * T // 4))
 acts = torch.rand((T, N), device=dev) * 2 - 1
 def timed(fn, reps):
     fn(); torch.cuda.synchronize(); t0 = time.perf_counter()
@@ -28,18 +43,18 @@ t_roll = timed(rollout, 3)
 def update(): agent.update(*batch["b"][:5])
 t_upd = timed(update, 2)
 # the framework path of the same update (autograd + torch.optim.Adam): what the fused step replaces
-agent_fw = PPO(env, horizon=T, seed=0, minibatch=max(2048, N * T // 4), fused_update=False)
+agent_fw = PPO(env, arch=ARCH, horizon=T, seed=0, minibatch=max(2048, N * T // 4), fused_update=False)
 def update_fw(): agent_fw.update(*batch["b"][:5])
 t_upd_fw = timed(update_fw, 1)
 # the same rollout double-buffered: the envs as two groups on their own streams, a group's policy kernel and env step queued
 # on its stream, no join inside the rollout (PPO.collect over a GroupedNetworkEnv: bit-identical data, tests/test_ppo.py)
 env.close()
 del agent_fw
-genv = pcc_rl_amd.GroupedNetworkEnv(N, 2, device=dev, seed=0)
+genv = pcc_rl_amd.GroupedNetworkEnv(N, 2, device=dev, seed=0, **ENV_KW)
 if os.environ.get("PCC_GROUP_SEND_WAVES"):
     for e in genv.groups:
         e.set_tuning(send_waves=float(os.environ["PCC_GROUP_SEND_WAVES"]))
-agent_g = PPO(genv, horizon=T, seed=0, minibatch=max(2048, N * T // 4))
+agent_g = PPO(genv, arch=ARCH, horizon=T, seed=0, minibatch=max(2048, N * T // 4))
 gbatch = {}
 def rollout_g(): gbatch["b"] = agent_g.collect()
 t_roll_g = timed(rollout_g, 3)

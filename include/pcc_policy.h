@@ -24,7 +24,8 @@ extern "C" {
  * mean_out, act_out, logp_out, value_out   [n_envs] each, device; any may be NULL
  * stream    HIP stream; nothing synchronizes
  * Returns 0 for every shape of the domain of pcc_ppo_supported (1 <= obs_dim <= 128, 1 <= h1, h2 <= 64: obs_dim, h1 and h2
- * are run-time values; --arch 32,16 at 30, 36, 3, 6, 12 or 60 observations runs a fully unrolled kernel); -1 bad arguments
+ * are run-time values; --arch 32,16 at 3, 6, 12, 30, 36 or 60 observations runs a fully unrolled kernel -- the table
+ * PCC_FIXED_OBS_LENGTHS of csrc/pcc_policy_dev.h, where PolicyLayout states the layout of `params` for every kernel); -1 bad arguments
  * (NULL obs / params, n_envs < 1, a hidden size outside 1 .. 64); -2 obs_dim outside 1 .. 128 (the caller falls back to its
  * framework path); -3 launch failure.
  */

@@ -1,6 +1,7 @@
 // pcc_mlp_tiles.h -- the PPO caller's two kernels for ANY policy of the supported domain (one sender, two tanh hidden layers,
 // 1 <= obs_dim <= 128, 1 <= h1, h2 <= 64): the tiled generalisation of ppo_grad_mfma_kernel (pcc_ppo.hip) and of the policy
-// forward (pcc_policy.hip).  obs_dim, h1, h2 are run-time values; a kernel is instantiated per TILE CLASS <DP, H1P, H2P>, the
+// forward (pcc_policy.hip); the parameter block's layout (PolicyLayout), tanh_fast, wave_sum and the Gaussian head are
+// pcc_policy_dev.h's, shared with those.  obs_dim, h1, h2 are run-time values; a kernel is instantiated per TILE CLASS <DP, H1P, H2P>, the
 // sizes rounded up (DP in {32, 64, 128}; (H1P, H2P) in {(32, 32), (64, 32), (64, 64)}), and everything between the real and the
 // padded size is zero: padded weights, biases and W3 entries are 0, so a padded unit is tanh_fast(0) = 0 exactly (exp(0) = 1,
 // rcp(2) = 0.5) and carries no gradient; padded rows / columns of dW are never stored.
@@ -31,6 +32,8 @@ constexpr int kTile = 32;           // samples per tile
 constexpr int kMaxGradBlocks = 256; // one workgroup per CU (LDS)
 
 using pcc::tanh_fast;
+using pcc::wave_sum;
+using Shape = pcc::PolicyLayout;   // the real sizes and the offsets inside one network's block of the parameter vector
 
 template <int DP, int H1P, int H2P>
 struct Cls {
@@ -46,13 +49,6 @@ struct Cls {
     static_assert(NW >= H1P * DP + H1P + H2P * H1P + 2 * H2P + 1, "the block's gradient is reduced in the weight area");
 };
 
-struct Shape {   // the real sizes and the offsets inside one network's block of the parameter vector (include/pcc_policy.h)
-    int D, h1, h2, W1, B1, W2, B2, W3, B3, N;
-    __host__ __device__ Shape(int D_, int h1_, int h2_) : D(D_), h1(h1_), h2(h2_) {
-        W1 = 0; B1 = h1 * D; W2 = B1 + h1; B2 = W2 + h2 * h1; W3 = B2 + h2; B3 = W3 + h2; N = B3 + 1;
-    }
-};
-
 __device__ __forceinline__ uint32_t c_row(int r, uint32_t lane) { return (uint32_t)(r & 3) + 8u * (uint32_t)(r >> 2) + 4u * (lane >> 5); }
 
 // LDS written by some lanes of a wavefront and read by others of it (LDS operations of a wavefront complete in order)
@@ -60,12 +56,6 @@ __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
 }
 
 // one network's parameters -> the workgroup's weight area, zero in every padded place (all threads; the caller synchronises)
@@ -322,18 +312,18 @@ __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void ppo_grad_
     __shared__ float lds[C::kLds];
     __shared__ float red[kWaves][4];
     const Shape s(D, n_h1, n_h2);
-    const int n_params = 2 * s.N + 1;
+    const int n_params = s.n_params();
     const uint32_t lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave, col = lane & 31u;
     float *Ws = lds, *Xs = lds + C::NW + wv * C::NWAVE + C::XS, *H1s = lds + C::NW + wv * C::NWAVE + C::H1S;
     float *Zs = lds + C::NW + wv * C::NWAVE + C::ZS, *Sc = lds + C::NW + wv * C::NWAVE + C::SC;
-    const float log_std = params[s.N];
+    const float log_std = params[s.log_std()];
     const float inv_std = __expf(-log_std);
     const float inv_n = 1.0f / (float)count;
     const int64_t n_tiles = (count + kTile - 1) / kTile;
     float *out_p = partial + (int64_t)blockIdx.x * (n_params + 4);
 #pragma unroll 1
     for (int pass = 0; pass < 2; pass++) {
-        load_weights<DP, H1P, H2P>(Ws, params + (pass ? s.N + 1 : 0), s, (int)threadIdx.x, kWaves * kWave);
+        load_weights<DP, H1P, H2P>(Ws, params + (pass ? s.vf() : 0), s, (int)threadIdx.x, kWaves * kWave);
         __syncthreads();
         GradAcc<H1P, H2P, DP> g;
 #pragma unroll
@@ -364,10 +354,10 @@ __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void ppo_grad_
             f32x16 h1[H1P / 32], h2[H2P / 32];
             const float out = tile_forward<DP, H1P, H2P>(Ws, Xs, H1s, Zs, lane, s, h1, h2);
             float dout = 0.0f;
-            if (pass == 0) {   // log-probability of the taken action, clipped surrogate
+            if (pass == 0) {   // log-probability of the taken action, clipped surrogate (ppo_grad_mfma_kernel's arithmetic: keep in step)
                 const float a = valid ? act[idx] : 0.0f, lp_old = valid ? logp_old[idx] : 0.0f, ad = valid ? adv[idx] : 0.0f;
                 const float z = (a - out) * inv_std;
-                const float lp = -0.5f * z * z - log_std - 0.918938533204672742f;
+                const float lp = pcc::gaussian_logp(z, log_std);
                 const float ratio = __expf(lp - lp_old);
                 const float lo = 1.0f - clip, hi = 1.0f + clip;
                 const float rc = fminf(fmaxf(ratio, lo), hi);
@@ -403,13 +393,13 @@ __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void ppo_grad_
             }
             __syncthreads();
         }
-        float *dst = out_p + (pass ? s.N + 1 : 0);
+        float *dst = out_p + (pass ? s.vf() : 0);
         for (int k = (int)threadIdx.x; k < s.N; k += kWaves * kWave) dst[k] = Ws[k];
         if (threadIdx.x == 0) {
             float a = red[0][0], b = red[0][1], c = red[0][2];
             for (int w = 1; w < kWaves; w++) { a += red[w][0]; b += red[w][1]; c += red[w][2]; }
             if (pass == 0) {
-                out_p[s.N] = a;
+                out_p[s.log_std()] = a;
                 out_p[n_params + 0] = b;
                 out_p[n_params + 2] = c;
             } else {
@@ -439,9 +429,9 @@ __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void policy_ac
     float *Ws = lds, *Xs = lds + C::NW + wv * C::NWAVE + C::XS, *H1s = lds + C::NW + wv * C::NWAVE + C::H1S;
     float *Zs = lds + C::NW + wv * C::NWAVE + C::ZS;
     const int net = (int)blockIdx.y;
-    load_weights<DP, H1P, H2P>(Ws, params + (net ? s.N + 1 : 0), s, (int)threadIdx.x, kWaves * kWave);
+    load_weights<DP, H1P, H2P>(Ws, params + (net ? s.vf() : 0), s, (int)threadIdx.x, kWaves * kWave);
     __syncthreads();
-    const float log_std = params[s.N];
+    const float log_std = params[s.log_std()];
     const int64_t n_tiles = (n + kTile - 1) / kTile;
 #pragma unroll 1
     for (int64_t tile = (int64_t)blockIdx.x * kWaves + wv; tile < n_tiles; tile += (int64_t)gridDim.x * kWaves) {
@@ -455,9 +445,8 @@ __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void policy_ac
             if (net == 0) {
                 const float eps = noise ? noise[i] : 0.0f;
                 if (mean_out) mean_out[i] = out;
-                if (act_out) act_out[i] = out + expf(log_std) * eps;
-                // log N(a; mu, sigma) = -eps^2 / 2 - log_std - log(2 pi) / 2
-                if (logp_out) logp_out[i] = -0.5f * eps * eps - log_std - 0.918938533204672742f;
+                if (act_out) act_out[i] = pcc::gaussian_act(out, log_std, eps);
+                if (logp_out) logp_out[i] = pcc::gaussian_logp(eps, log_std);
             } else if (value_out) {
                 value_out[i] = out;
             }
@@ -483,8 +472,9 @@ struct ActArgs {
     float *mean_out, *act_out, *logp_out, *value_out;
 };
 
+// one tile class's launch: the same name for both kernels, told apart by the argument block
 template <int DP, int H1P, int H2P>
-inline int launch_grad_class(const GradArgs &a, hipStream_t st, int *blocks_out) {
+inline int launch_class(const GradArgs &a, hipStream_t st, int *blocks_out) {
     using C = Cls<DP, H1P, H2P>;
     const int64_t tiles = (a.count + kTile - 1) / kTile;
     int64_t blocks = (tiles + C::kWaves - 1) / C::kWaves;
@@ -496,7 +486,7 @@ inline int launch_grad_class(const GradArgs &a, hipStream_t st, int *blocks_out)
 }
 
 template <int DP, int H1P, int H2P>
-inline int launch_act_class(const ActArgs &a, hipStream_t st) {
+inline int launch_class(const ActArgs &a, hipStream_t st, int *) {
     using C = Cls<DP, H1P, H2P>;
     const int64_t tiles = (a.n + kTile - 1) / kTile;
     int64_t blocks = (tiles + C::kWaves - 1) / C::kWaves;
@@ -506,18 +496,12 @@ inline int launch_act_class(const ActArgs &a, hipStream_t st) {
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-template <int DP>
-inline int launch_grad_d(const GradArgs &a, hipStream_t st, int *blocks_out) {
-    if (a.h1 <= 32 && a.h2 <= 32) return launch_grad_class<DP, 32, 32>(a, st, blocks_out);
-    if (a.h2 <= 32) return launch_grad_class<DP, 64, 32>(a, st, blocks_out);
-    return launch_grad_class<DP, 64, 64>(a, st, blocks_out);
-}
-
-template <int DP>
-inline int launch_act_d(const ActArgs &a, hipStream_t st) {
-    if (a.h1 <= 32 && a.h2 <= 32) return launch_act_class<DP, 32, 32>(a, st);
-    if (a.h2 <= 32) return launch_act_class<DP, 64, 32>(a, st);
-    return launch_act_class<DP, 64, 64>(a, st);
+// the hidden class of (h1, h2) at observation class DP, for either argument block
+template <int DP, class Args>
+inline int launch_d(const Args &a, hipStream_t st, int *blocks_out = nullptr) {
+    if (a.h1 <= 32 && a.h2 <= 32) return launch_class<DP, 32, 32>(a, st, blocks_out);
+    if (a.h2 <= 32) return launch_class<DP, 64, 32>(a, st, blocks_out);
+    return launch_class<DP, 64, 64>(a, st, blocks_out);
 }
 
 // the domain both kernels cover (pcc_ppo_supported)

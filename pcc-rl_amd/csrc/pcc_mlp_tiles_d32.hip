@@ -3,6 +3,6 @@
 #include "pcc_mlp_tiles.h"
 
 namespace pcc_tiles {
-int launch_grad_d32(const GradArgs &a, hipStream_t st, int *blocks_out) { return launch_grad_d<32>(a, st, blocks_out); }
-int launch_act_d32(const ActArgs &a, hipStream_t st) { return launch_act_d<32>(a, st); }
+int launch_grad_d32(const GradArgs &a, hipStream_t st, int *blocks_out) { return launch_d<32>(a, st, blocks_out); }
+int launch_act_d32(const ActArgs &a, hipStream_t st) { return launch_d<32>(a, st); }
 }  // namespace pcc_tiles

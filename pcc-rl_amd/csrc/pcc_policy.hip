@@ -5,10 +5,11 @@
 // not starved by a dozen small framework launches per step.  One lane per env; the few thousand
 // parameters sit in LDS, every lane walks them in the same order (broadcast reads, no bank conflicts);
 // fp32 like the framework path it replaces.  No MFMA: 65 536 x ~3 kFLOP is microseconds of plain FMAs.
-// That holds for the kernels of this file (the reference's --arch 32,16 fully unrolled at six observation lengths, and the
-// older generic kernel at those lengths below 8 192 parameters).  Every other shape of the supported domain (up to 128
-// observations, hidden layers up to 64 wide, run-time sizes) takes policy_act_tiled_kernel (pcc_mlp_tiles.h): the gradient
-// kernel's MFMA forward, weights and activations in LDS, no private arrays.
+// That holds for the kernels of this file, both built for the observation lengths of PCC_FIXED_OBS_LENGTHS (pcc_policy_dev.h):
+// the reference's --arch 32,16 fully unrolled, and the older generic kernel for other policies below 8 192 parameters.  Every
+// other shape of the supported domain (up to 128 observations, hidden layers up to 64 wide, run-time sizes) takes
+// policy_act_tiled_kernel (pcc_mlp_tiles.h): the gradient kernel's MFMA forward, weights and activations in LDS, no private
+// arrays.  The parameter block's layout, tanh_fast and the Gaussian head are pcc_policy_dev.h's.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -19,10 +20,15 @@
 
 namespace {
 
+using pcc::PolicyLayout;
+using pcc::tanh_fast;   // (shared with the rollout epilogue of the env's kernels, which must give these kernels' bits)
+
 constexpr int kMaxParams = 8192;   // floats of both networks
 constexpr int kMaxHidden = 64;
 
-// parameter block, floats: pi {W1[h1][D], b1[h1], W2[h2][h1], b2[h2], W3[h2], b3, log_std}, then vf {same without log_std}
+// one network (p = its first float of the parameter block) on one observation row.  The pointers are chained as they always
+// were, not taken from PolicyLayout's offsets: with run-time sizes that folds the address arithmetic differently and changes this
+// old kernel's register counts (policy_act_kernel<3>: 38 -> 36 scalar registers) -- it is left as it was generated.
 __device__ __forceinline__ float mlp_forward(const float *p, const float *x, int D, int h1, int h2, float *z1, float *z2) {
     const float *W1 = p, *b1 = W1 + h1 * D, *W2 = b1 + h1, *b2 = W2 + h2 * h1, *W3 = b2 + h2, *b3 = W3 + h2;
     for (int j = 0; j < h1; j++) {
@@ -53,27 +59,24 @@ __global__ __launch_bounds__(256) void policy_act_kernel(const float *obs, int64
 #pragma unroll
     for (int k = 0; k < D; k++) x[k] = obs[i * D + k];
     float z1[kMaxHidden], z2[kMaxHidden];
-    const int n_pi = h1 * D + h1 + h2 * h1 + h2 + h2 + 1;   // without log_std
     const float mu = mlp_forward(sp, x, D, h1, h2, z1, z2);
-    const float log_std = sp[n_pi];
-    const float v = mlp_forward(sp + n_pi + 1, x, D, h1, h2, z1, z2);
+    const PolicyLayout L(D, h1, h2);   // (after the first forward: placed above it, this old kernel's scalar code moves)
+    const float log_std = sp[L.log_std()];
+    const float v = mlp_forward(sp + L.vf(), x, D, h1, h2, z1, z2);
     const float eps = noise ? noise[i] : 0.0f;
-    const float a = mu + expf(log_std) * eps;
-    // log N(a; mu, sigma) = -eps^2 / 2 - log_std - log(2 pi) / 2
+    const float a = pcc::gaussian_act(mu, log_std, eps);
     if (mean_out) mean_out[i] = mu;
     if (act_out) act_out[i] = a;
-    if (logp_out) logp_out[i] = -0.5f * eps * eps - log_std - 0.918938533204672742f;
+    if (logp_out) logp_out[i] = pcc::gaussian_logp(eps, log_std);
     if (value_out) value_out[i] = v;
 }
-
-// tanh_fast: pcc_policy_dev.h (shared with the rollout epilogue of the env's kernels, which must give this kernel's bits)
-using pcc::tanh_fast;
 
 // The reference's own sizes (--arch 32,16) with everything a compile-time constant: the hidden activations stay in
 // registers (the generic kernel above indexes z1[j] with a run-time j: scratch memory), the loops unroll.
 template <int D, int H1, int H2>
 __device__ __forceinline__ float mlp_forward_fixed(const float *p, const float (&x)[D]) {
-    const float *W1 = p, *b1 = W1 + H1 * D, *W2 = b1 + H1, *b2 = W2 + H2 * H1, *W3 = b2 + H2, *b3 = W3 + H2;
+    constexpr PolicyLayout L(D, H1, H2);
+    const float *W1 = p + L.W1, *b1 = p + L.B1, *W2 = p + L.W2, *b2 = p + L.B2, *W3 = p + L.W3, *b3 = p + L.B3;
     float z1[H1], z2[H2];
 #pragma unroll
     for (int j = 0; j < H1; j++) {
@@ -112,16 +115,16 @@ __global__ __launch_bounds__(256) void policy_act_fixed_kernel(const float *__re
     float x[D];
 #pragma unroll
     for (int k = 0; k < D; k++) x[k] = obs[i * D + k];
-    constexpr int n_pi = H1 * D + H1 + H2 * H1 + H2 + H2 + 1;   // without log_std
+    constexpr PolicyLayout L(D, H1, H2);
     if (blockIdx.y == 0) {
         const float mu = mlp_forward_fixed<D, H1, H2>(params, x);
-        const float log_std = params[n_pi];
+        const float log_std = params[L.log_std()];
         const float eps = noise ? noise[i] : 0.0f;
         if (mean_out) mean_out[i] = mu;
-        if (act_out) act_out[i] = mu + expf(log_std) * eps;
-        if (logp_out) logp_out[i] = -0.5f * eps * eps - log_std - 0.918938533204672742f;
+        if (act_out) act_out[i] = pcc::gaussian_act(mu, log_std, eps);
+        if (logp_out) logp_out[i] = pcc::gaussian_logp(eps, log_std);
     } else {
-        const float v = mlp_forward_fixed<D, H1, H2>(params + n_pi + 1, x);
+        const float v = mlp_forward_fixed<D, H1, H2>(params + L.vf(), x);
         if (value_out) value_out[i] = v;
     }
 }
@@ -133,46 +136,25 @@ extern "C" int pcc_policy_act(const float *obs, int64_t n_envs, int obs_dim, con
                               void *stream) {
     if (!obs || !params || n_envs < 1) return -1;
     if (h1 < 1 || h2 < 1 || h1 > kMaxHidden || h2 > kMaxHidden) return -1;
-    const int n_net = h1 * obs_dim + h1 + h2 * h1 + h2 + h2 + 1;
-    const int n_params = 2 * n_net + 1;
-    const bool old_length = obs_dim == 30 || obs_dim == 36 || obs_dim == 3 || obs_dim == 6 || obs_dim == 12 || obs_dim == 60;
-    if (n_params > kMaxParams || !old_length) {   // what the kernels of this file refuse: the tiled kernel (-2 outside its domain)
+    const int n_params = PolicyLayout(obs_dim, h1, h2).n_params();
+    if (n_params > kMaxParams || !pcc::fixed_act_length(obs_dim)) {   // what the kernels of this file refuse: the tiled kernel (-2 outside its domain)
         const pcc_tiles::ActArgs a{obs, n_envs, obs_dim, h1, h2, params, noise, mean_out, act_out, logp_out, value_out};
         return pcc_tiles::launch_act(a, static_cast<hipStream_t>(stream));
     }
     const dim3 grid((unsigned)((n_envs + 255) / 256)), block(256);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (h1 == 32 && h2 == 16) {   // the reference's --arch: the fully unrolled build
-        switch (obs_dim) {
-#define PCC_POLICY_FIXED(DD)                                                                                             \
-    case DD:                                                                                                             \
-        hipLaunchKernelGGL((policy_act_fixed_kernel<DD, 32, 16>), dim3(grid.x, 2), block, 0, st, obs, n_envs, params, n_params, noise, \
-                           mean_out, act_out, logp_out, value_out);                                                     \
-        return hipGetLastError() == hipSuccess ? 0 : -3;
-            PCC_POLICY_FIXED(30)
-            PCC_POLICY_FIXED(36)
-            PCC_POLICY_FIXED(3)
-            PCC_POLICY_FIXED(6)
-            PCC_POLICY_FIXED(12)
-            PCC_POLICY_FIXED(60)
-#undef PCC_POLICY_FIXED
-            default: break;
-        }
+    const bool fixed_net = h1 == 32 && h2 == 16;   // the reference's --arch: the fully unrolled build
+    // the observation length is a compile-time constant of both kernels (unrolled loads)
+#define PCC_POLICY_CASE(DD)                                                                                                          \
+    if (obs_dim == DD) {                                                                                                             \
+        if (fixed_net)                                                                                                               \
+            hipLaunchKernelGGL((policy_act_fixed_kernel<DD, 32, 16>), dim3(grid.x, 2), block, 0, st, obs, n_envs, params, n_params, noise, \
+                               mean_out, act_out, logp_out, value_out);                                                             \
+        else                                                                                                                         \
+            hipLaunchKernelGGL(policy_act_kernel<DD>, grid, block, 0, st, obs, n_envs, params, n_params, h1, h2, noise, mean_out,    \
+                               act_out, logp_out, value_out);                                                                       \
     }
-    switch (obs_dim) {   // the observation length is a compile-time constant of the unrolled loads
-#define PCC_POLICY_CASE(DD)                                                                                              \
-    case DD:                                                                                                             \
-        hipLaunchKernelGGL(policy_act_kernel<DD>, grid, block, 0, st, obs, n_envs, params, n_params, h1, h2, noise, mean_out, \
-                           act_out, logp_out, value_out);                                                               \
-        break;
-        PCC_POLICY_CASE(30)   // history 10 x 3 features: the reference's default observation (ns:382-388)
-        PCC_POLICY_CASE(36)   // history 3 x all 12 features
-        PCC_POLICY_CASE(3)
-        PCC_POLICY_CASE(6)
-        PCC_POLICY_CASE(12)
-        PCC_POLICY_CASE(60)
+    PCC_FIXED_OBS_LENGTHS(PCC_POLICY_CASE)
 #undef PCC_POLICY_CASE
-        default: return -2;   // (not reached: the lengths above)
-    }
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

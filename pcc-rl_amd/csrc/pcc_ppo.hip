@@ -16,7 +16,8 @@
 //   ppo_adam_kernel   sums the partial gradients in a fixed order (deterministic), adds the entropy
 //                     term, applies Adam (torch.optim.Adam's arithmetic), writes the parameters in place.
 //
-// ppo_grad_mfma_kernel is built for --arch 32,16 at 30, 12, 6 and 3 observations; every other shape of the supported domain
+// ppo_grad_mfma_kernel is built for --arch 32,16 at the observation lengths of PCC_MFMA_OBS_LENGTHS (pcc_policy_dev.h: the layout
+// of the parameter block, tanh_fast and the Gaussian log-probability are that header's too); every other shape of the supported domain
 // (pcc_ppo_supported: up to 128 observations, hidden layers up to 64 wide) takes ppo_grad_tiled_kernel (pcc_mlp_tiles.h), the
 // tiled generalisation with run-time sizes, which writes partial gradients of the same layout for the same ppo_adam_kernel.
 //
@@ -38,25 +39,12 @@ constexpr int kWave = 64;
 constexpr int kWavesPerBlock = 2;
 constexpr int kMaxBlocks = 512;   // 2 wavefronts each: one per SIMD of the chip, which is what ~480 registers allow
 
-template <int D, int H1, int H2>
-struct Net {  // offsets inside one network's block of the parameter vector (include/pcc_policy.h)
-    static constexpr int W1 = 0, B1 = H1 * D, W2 = B1 + H1, B2 = W2 + H2 * H1, W3 = B2 + H2, B3 = W3 + H2, N = B3 + 1;
-};
-
-// tanh(x) = 1 - 2 / (exp(2x) + 1): absolute error ~1e-7 (one rounding of the quotient against 1), saturates cleanly
-__device__ __forceinline__ float tanh_fast(float x) {
-    const float e = __expf(2.0f * x);
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
+using pcc::PolicyLayout;
+using pcc::tanh_fast;
+using pcc::wave_sum;
 
 constexpr int kS33 = 33, kS17 = 17;               // row strides of the sample-major LDS buffers: conflict-free both ways
 constexpr int kBufFloats = kWave * kS33;          // one [64][33] operand buffer
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, kWave);
-    return v;
-}
 
 // ======================================================================================
 // ppo_grad_mfma_kernel: a layer is a small GEMM per tile of 64 samples: the weights are the B
@@ -93,21 +81,21 @@ struct MfmaAcc {       // one network's gradient sums of a wavefront
 
 template <int D, int H1, int H2>
 __device__ __forceinline__ void mfma_load_weights(MfmaWeights &w, const float *__restrict__ p, uint32_t lane) {
-    using L = Net<D, H1, H2>;
+    constexpr PolicyLayout L(D, H1, H2);
 #pragma unroll
     for (int t = 0; t < 16; t++) {
         const uint32_t k = 2u * t + (lane >> 5);
-        w.w1b[t] = k < (uint32_t)D ? p[L::W1 + (lane & 31u) * D + k] : 0.0f;
+        w.w1b[t] = k < (uint32_t)D ? p[L.W1 + (lane & 31u) * D + k] : 0.0f;
     }
 #pragma unroll
     for (int t = 0; t < 8; t++) {
-        w.w2b[t] = p[L::W2 + (lane & 15u) * H1 + 4u * t + (lane >> 4)];
-        w.w2c[t] = p[L::W2 + (2u * t + (lane >> 5)) * H1 + (lane & 31u)];
+        w.w2b[t] = p[L.W2 + (lane & 15u) * H1 + 4u * t + (lane >> 4)];
+        w.w2c[t] = p[L.W2 + (2u * t + (lane >> 5)) * H1 + (lane & 31u)];
     }
-    w.b1c = p[L::B1 + (lane & 31u)];
-    w.b2c = p[L::B2 + (lane & 15u)];
-    w.w3c = p[L::W3 + (lane & 15u)];
-    w.b3 = p[L::B3];
+    w.b1c = p[L.B1 + (lane & 31u)];
+    w.b2c = p[L.B2 + (lane & 15u)];
+    w.w3c = p[L.W3 + (lane & 15u)];
+    w.b3 = p[L.B3];
 }
 
 // forward of one network over the tile: on return h1 (C layout of two 32x32 tiles) and h2 (C layout of four 16x16 tiles) hold
@@ -212,28 +200,28 @@ __device__ __forceinline__ void mfma_backward(const MfmaWeights &w, MfmaAcc &g, 
 
 template <int D, int H1, int H2>
 __device__ __forceinline__ void mfma_acc_store(const MfmaAcc &acc, float *g, const uint32_t lane, const bool add) {
-    using L = Net<D, H1, H2>;
+    constexpr PolicyLayout L(D, H1, H2);
     auto put = [&](int idx, float v) { g[idx] = add ? g[idx] + v : v; };
     const uint32_t col = lane & 31u;
 #pragma unroll
     for (int r = 0; r < 16; r++) {
         const uint32_t row = (uint32_t)(r & 3) + 8u * (uint32_t)(r >> 2) + 4u * (lane >> 5);
-        if (col < (uint32_t)D) put(L::W1 + (int)row * D + (int)col, acc.w1[r]);
+        if (col < (uint32_t)D) put(L.W1 + (int)row * D + (int)col, acc.w1[r]);
     }
 #pragma unroll
     for (int r = 0; r < 4; r++) {
         const uint32_t row = 4u * (lane >> 4) + (uint32_t)r, c = lane & 15u;
-        put(L::W2 + (int)row * H1 + (int)c, acc.w2a[r]);
-        put(L::W2 + (int)row * H1 + 16 + (int)c, acc.w2b[r]);
+        put(L.W2 + (int)row * H1 + (int)c, acc.w2a[r]);
+        put(L.W2 + (int)row * H1 + 16 + (int)c, acc.w2b[r]);
     }
     float b1 = acc.b1, b2 = acc.b2, w3 = acc.w3;
     b1 += __shfl_xor(b1, 32, kWave);
     b2 += __shfl_xor(b2, 16, kWave); b2 += __shfl_xor(b2, 32, kWave);
     w3 += __shfl_xor(w3, 16, kWave); w3 += __shfl_xor(w3, 32, kWave);
     const float b3 = wave_sum(acc.b3);
-    if (lane < 32u) put(L::B1 + (int)lane, b1);
-    if (lane < 16u) { put(L::B2 + (int)lane, b2); put(L::W3 + (int)lane, w3); }
-    if (lane == 0u) put(L::B3, b3);
+    if (lane < 32u) put(L.B1 + (int)lane, b1);
+    if (lane < 16u) { put(L.B2 + (int)lane, b2); put(L.W3 + (int)lane, w3); }
+    if (lane == 0u) put(L.B3, b3);
 }
 
 template <int D, int H1, int H2>
@@ -241,9 +229,9 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, 1) void ppo_grad_mfma_kernel
     const float *__restrict__ obs, const float *__restrict__ act, const float *__restrict__ logp_old,
     const float *__restrict__ adv, const float *__restrict__ ret, const int64_t *__restrict__ perm, int64_t start,
     int64_t count, const float *__restrict__ params, float clip, float *__restrict__ partial) {
-    using L = Net<D, H1, H2>;
+    constexpr PolicyLayout L(D, H1, H2);
     static_assert(H1 == 32 && H2 == 16 && D <= 32, "the MFMA tiles are the reference's --arch 32,16 on at most 32 features");
-    constexpr int kPi = 0, kLogStd = L::N, kVf = L::N + 1, kParams = 2 * L::N + 1;
+    constexpr int kPi = 0, kLogStd = L.log_std(), kVf = L.vf(), kParams = L.n_params();
     static_assert(kParams + 4 <= kMfmaWaveLds, "the block's gradient is reduced in a wavefront's LDS buffers");
     __shared__ float lds[kWavesPerBlock * kMfmaWaveLds];
     const uint32_t lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
@@ -294,7 +282,9 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, 1) void ppo_grad_mfma_kernel
         __builtin_amdgcn_wave_barrier();
         const int64_t left = count - tile * kWave;   // samples of this tile that exist
         float h1[2][16], h2[4][4], out[4][4], dout[4][4];
-        // ---- policy network: log-probability of the taken action, clipped surrogate
+        // ---- policy network: log-probability of the taken action, clipped surrogate.  The per-sample arithmetic below is
+        // written out in ppo_grad_tiled_kernel (pcc_mlp_tiles.h) too and the two are kept in step by hand: as one shared
+        // function (sums by reference) the results are the same but two tiled instantiations change their register counts.
         mfma_forward<D, H1, H2>(wpi, Xs, H1s, lane, h1, h2, out);
 #pragma unroll
         for (int T4 = 0; T4 < 4; T4++) {
@@ -304,7 +294,7 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, 1) void ppo_grad_mfma_kernel
                 const bool valid = (int64_t)m < left;
                 const float a = Sc[m], lp_old = Sc[kWave + m], ad = Sc[2 * kWave + m];
                 const float z = (a - out[T4][r]) * inv_std;
-                const float lp = -0.5f * z * z - log_std - 0.918938533204672742f;
+                const float lp = pcc::gaussian_logp(z, log_std);
                 const float ratio = __expf(lp - lp_old);
                 const float lo = 1.0f - clip, hi = 1.0f + clip;
                 const float rc = fminf(fmaxf(ratio, lo), hi);
@@ -416,16 +406,13 @@ __global__ void gae_kernel(const float *__restrict__ rew, const float *__restric
 }  // namespace
 
 // the shapes ppo_grad_mfma_kernel is instantiated for; the rest of the domain goes to the tiled kernel
-static bool mfma_fixed_shape(int obs_dim, int h1, int h2) {
-    return h1 == 32 && h2 == 16 && (obs_dim == 30 || obs_dim == 3 || obs_dim == 6 || obs_dim == 12);
-}
+static bool mfma_fixed_shape(int obs_dim, int h1, int h2) { return h1 == 32 && h2 == 16 && pcc::mfma_grad_length(obs_dim); }
 
 extern "C" int pcc_ppo_supported(int obs_dim, int h1, int h2) { return pcc_tiles::in_domain(obs_dim, h1, h2) ? 1 : 0; }
 
 extern "C" int pcc_ppo_scratch_floats(int obs_dim, int h1, int h2) {
-    const int n_net = h1 * obs_dim + h1 + h2 * h1 + h2 + h2 + 1;
     const int blocks = mfma_fixed_shape(obs_dim, h1, h2) || !pcc_tiles::in_domain(obs_dim, h1, h2) ? kMaxBlocks : pcc_tiles::kMaxGradBlocks;
-    return blocks * (2 * n_net + 1 + 4);
+    return blocks * (PolicyLayout(obs_dim, h1, h2).n_params() + 4);
 }
 
 extern "C" int pcc_ppo_minibatch_step(const float *obs, const float *act, const float *logp_old, const float *adv,
@@ -435,8 +422,7 @@ extern "C" int pcc_ppo_minibatch_step(const float *obs, const float *act, const 
                                       float *grad_out, float *stats_out, void *stream) {
     if (!obs || !act || !logp_old || !adv || !ret || !params || !scratch || count < 1 || start < 0) return -1;
     if (lr != 0.0f && (!adam_m || !adam_v || adam_step < 1)) return -1;
-    const int n_net = h1 * obs_dim + h1 + h2 * h1 + h2 + h2 + 1;
-    const int n_params = 2 * n_net + 1;
+    const PolicyLayout L(obs_dim, h1, h2);
     hipStream_t st = static_cast<hipStream_t>(stream);
     int64_t blocks;
     if (mfma_fixed_shape(obs_dim, h1, h2)) {
@@ -444,19 +430,12 @@ extern "C" int pcc_ppo_minibatch_step(const float *obs, const float *act, const 
         blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
         if (blocks > kMaxBlocks) blocks = kMaxBlocks;
         const dim3 grid((unsigned)blocks), block(kWavesPerBlock * kWave);
-        switch (obs_dim) {
 #define PCC_PPO_CASE(DD)                                                                                                   \
-    case DD:                                                                                                               \
+    if (obs_dim == DD)                                                                                                     \
         hipLaunchKernelGGL((ppo_grad_mfma_kernel<DD, 32, 16>), grid, block, 0, st, obs, act, logp_old, adv, ret, perm, start, \
-                           count, params, clip, scratch);                                                                 \
-        break;
-            PCC_PPO_CASE(30)   // history 10 x 3 features: the reference's default observation (ns:382-388)
-            PCC_PPO_CASE(3)
-            PCC_PPO_CASE(6)
-            PCC_PPO_CASE(12)
+                           count, params, clip, scratch);
+        PCC_MFMA_OBS_LENGTHS(PCC_PPO_CASE)
 #undef PCC_PPO_CASE
-            default: return -2;
-        }
     } else {   // any other shape of the domain: the tiled kernel (-2 outside: the caller falls back to its framework path)
         const pcc_tiles::GradArgs a{obs, act, logp_old, adv, ret, perm, start, count, obs_dim, h1, h2, params, clip, scratch};
         int nb = 0;
@@ -467,8 +446,8 @@ extern "C" int pcc_ppo_minibatch_step(const float *obs, const float *act, const 
     if (hipGetLastError() != hipSuccess) return -3;
     const float bias1 = lr != 0.0f ? 1.0f - powf(beta1, (float)adam_step) : 1.0f;
     const float bias2 = lr != 0.0f ? sqrtf(1.0f - powf(beta2, (float)adam_step)) : 1.0f;
-    hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((n_params + 4 + 15) / 16)), dim3(256), 0, st, scratch, (int)blocks,
-                       n_params, n_net, ent_coef, params, adam_m, adam_v, lr, beta1, beta2, eps, bias1, bias2,
+    hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((L.n_params() + 4 + 15) / 16)), dim3(256), 0, st, scratch, (int)blocks,
+                       L.n_params(), L.log_std(), ent_coef, params, adam_m, adam_v, lr, beta1, beta2, eps, bias1, bias2,
                        1.0f / (float)count, grad_out, stats_out);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }

@@ -1251,15 +1251,15 @@ int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps
     };
     // The policy inside the env's launches: the reference's --arch 32,16 (at an observation length the stand-alone FIXED kernel has
     // an instantiation for: the epilogue gives its bits; other hidden sizes of pcc_policy_act's domain run launch by launch), one sender, the send + retire launches (no event loop, no one-launch step)
-    const bool fixed_len = D == 3 || D == 6 || D == 12 || D == 30 || D == 36 || D == 60;
+    const bool fixed_len = fixed_act_length(D);
     // --arch 32,16 keeps the domain it had: its rollouts are the fixed kernel's (the in-step paths below give that kernel's bits),
     // and an observation length without one stays refused, before anything is stepped (tests/test_rollout.py pins the refusal)
     if (h1 == kPolH1 && h2 == kPolH2 && !fixed_len)
-        return fail(PCC_EINVAL, "pcc_rollout: hidden sizes (%d, %d) run at observation length 3, 6, 12, 30, 36 or 60 (the fixed policy kernel); "
+        return fail(PCC_EINVAL, "pcc_rollout: hidden sizes (%d, %d) run at observation length " PCC_FIXED_OBS_LENGTHS_TEXT " (the fixed policy kernel); "
                                 "no rollout at observation length %d -- step it with pcc_policy_act + pcc_step", h1, h2, D);
     const bool fixed_net = h1 == kPolH1 && h2 == kPolH2 && fixed_len;
     const bool in_step = fixed_net && d.ns == 1 && !d.engine;
-    PolicyArgs pa{params, pol_params(D), D, act_rows, 0, noise, act, logp_out, value_out};
+    PolicyArgs pa{params, PolicyLayout(D, kPolH1, kPolH2).n_params(), D, act_rows, 0, noise, act, logp_out, value_out};
     if (in_step && d.n >= (int64_t)sim->list_min_envs && !sim->fused && sim->rollout_epilogue) {
         // Epilogue path (PCC_TUNE_ROLLOUT_EPILOGUE; off by default: measured slower than the launches it replaces):
         // the retire launch of step t computes the action of step t + 1 -- unless reset launches follow the step (they rewrite

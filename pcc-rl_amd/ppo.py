@@ -17,10 +17,13 @@ fp32-MFMA gradient kernel and the Adam step (pcc_ppo.hip: pcc_ppo_minibatch_step
 the return; and what the whole loop costs next to the env alone (tools/ppo_throughput.py,
 profiles/r04_v2_ppo_throughput.json).
 """
+import ctypes
 import math
 
 import torch
 from torch import nn
+
+from .env import _ptr
 
 
 class AlignedLinear(nn.Linear):
@@ -104,23 +107,27 @@ class MlpPolicy(nn.Module):
         assert off == flat.numel()
         return flat
 
+    @property
+    def hidden(self):
+        """The two hidden sizes (h1, h2) -- what the HIP library's policy kernels take -- or None when the policy is not two
+        hidden layers with one action."""
+        out = [m.out_features for m in self.pi if isinstance(m, nn.Linear)]
+        return (out[0], out[1]) if len(out) == 3 and out[2] == 1 else None
+
     def fused_ok(self, obs):
         """Whether pcc_policy_act covers this policy and observation batch (two hidden layers, one action, fp32 on the GPU)."""
-        linears = [m for m in self.pi if isinstance(m, nn.Linear)]
-        return len(linears) == 3 and linears[2].out_features == 1 and obs.is_cuda and obs.dtype == torch.float32
+        return self.hidden is not None and obs.is_cuda and obs.dtype == torch.float32
 
     @torch.no_grad()
     def act_fused(self, obs, stochastic=True, params=None, noise=None, out=None):
         """act() as ONE kernel launch of the HIP library; returns (action [N, 1], log-probability [N], value [N]) like act().
         A rollout loop passes `params` (flat_params(), built once per rollout -- it is a 13-tensor torch.cat), its own
         `noise` row and `out` = (action, logp, value) rows of its buffers, so that a step adds no framework launch."""
-        import ctypes
-
         from .native import lib
         if not self.fused_ok(obs):
             _warn_once("the policy forward runs on the framework path (no pcc_policy_act for this policy / observation batch)")
             return self.act(obs, stochastic)
-        linears = [m for m in self.pi if isinstance(m, nn.Linear)]
+        h1, h2 = self.hidden
         n, D = obs.shape
         if params is None:
             params = self.flat_params()
@@ -131,13 +138,12 @@ class MlpPolicy(nn.Module):
             logp, v = torch.empty_like(a), torch.empty_like(a)
         else:
             a, logp, v = out
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
-        rc = lib().pcc_policy_act(ptr(obs.contiguous()), n, D, ptr(params), linears[0].out_features, linears[1].out_features,
-                                  ptr(noise if stochastic else None), None, ptr(a), ptr(logp), ptr(v),
+        rc = lib().pcc_policy_act(_ptr(obs.contiguous()), n, D, _ptr(params), h1, h2,
+                                  _ptr(noise if stochastic else None), None, _ptr(a), _ptr(logp), _ptr(v),
                                   ctypes.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream))
         if rc != 0:   # a shape outside the library's domain (include/pcc_policy.h: pcc_ppo_supported)
             _warn_once("pcc_policy_act has no kernel for %d observations x hidden %d-%d: the policy forward runs on the framework "
-                       "path (several times slower)" % (D, linears[0].out_features, linears[1].out_features))
+                       "path (several times slower)" % (D, h1, h2))
             a2, logp2, v2 = self.act(obs, stochastic)
             if out is not None:
                 a.copy_(a2.reshape(-1)); logp.copy_(logp2); v.copy_(v2)
@@ -163,8 +169,6 @@ def gae(rewards, values, dones, last_value, gamma=0.99, lam=0.95):
 
 def gae_fused(rewards, values, dones, last_value, gamma=0.99, lam=0.95):
     """gae() as one launch of the HIP library (pcc_gae: thread = env, T steps backwards) for fp32 [T, N] rows on the GPU."""
-    import ctypes
-
     from .native import lib
     if not (rewards.is_cuda and rewards.dtype == torch.float32 and rewards.dim() == 2):
         return gae(rewards, values, dones, last_value, gamma, lam)
@@ -172,8 +176,7 @@ def gae_fused(rewards, values, dones, last_value, gamma=0.99, lam=0.95):
     rewards, values, last_value = rewards.contiguous(), values.contiguous(), last_value.contiguous().float()
     d8 = dones.contiguous().view(torch.uint8) if dones.dtype == torch.bool else dones.to(torch.uint8).contiguous()
     adv, ret = torch.empty_like(rewards), torch.empty_like(rewards)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr())
-    rc = lib().pcc_gae(ptr(rewards), ptr(values), ptr(d8), ptr(last_value), T, N, gamma, lam, ptr(adv), ptr(ret),
+    rc = lib().pcc_gae(_ptr(rewards), _ptr(values), _ptr(d8), _ptr(last_value), T, N, gamma, lam, _ptr(adv), _ptr(ret),
                        ctypes.c_void_p(torch.cuda.current_stream(rewards.device).cuda_stream))
     if rc != 0:
         raise RuntimeError("pcc_gae failed (%d)" % rc)
@@ -233,11 +236,11 @@ class PPO(object):
 
     def _fused_update_ok(self):
         env = self.env
-        arch = [m.out_features for m in self.policy.pi if isinstance(m, nn.Linear)]
-        if not (torch.device(env.device).type == "cuda" and len(arch) == 3 and arch[2] == 1 and env.n_senders == 1):
+        hidden = self.policy.hidden
+        if not (torch.device(env.device).type == "cuda" and hidden is not None and env.n_senders == 1):
             return False
         from .native import lib
-        return lib().pcc_ppo_supported(int(env.obs_dim), arch[0], arch[1]) == 1
+        return lib().pcc_ppo_supported(int(env.obs_dim), hidden[0], hidden[1]) == 1
 
     def collect(self):
         """One rollout of `horizon` steps of every env.  The policy kernel reads the observation row the env wrote and
@@ -258,7 +261,7 @@ class PPO(object):
             raise ValueError("PPO(policy_in_step=True) needs the fused rollout: a two-hidden-layer policy, one sender, on the GPU")
         if self.policy_in_step:
             # the whole horizon as one pcc_rollout per env (group): the same noise, parameters and rows as the loop below
-            arch = tuple(m.out_features for m in self.policy.pi if isinstance(m, nn.Linear))[:2]
+            arch = self.policy.hidden
             params = self.policy.flat_params()
             noise = torch.randn((T, N), device=dev)
             u8 = done_b.view(torch.uint8)
@@ -353,21 +356,18 @@ class PPO(object):
     def minibatch_step_fused(self, obs_f, act_f, logp_f, adv_f, ret_f, perm, start, count, lr=None, grad_out=None):
         """One optimiser step on samples perm[start : start + count] of the flattened rollout as two launches of the HIP
         library (include/pcc_policy.h: pcc_ppo_minibatch_step).  lr=0: gradient only (into grad_out)."""
-        import ctypes
-
         from .native import lib
         lr = self.lr if lr is None else lr
         if start < 0 or count < 1 or start + count > (perm.numel() if perm is not None else obs_f.shape[0]):
             raise ValueError("minibatch [%d, %d) outside the rollout" % (start, start + count))
         if lr != 0.0:
             self.adam_t += 1
-        ptr = lambda t: None if t is None else ctypes.c_void_p(t.data_ptr())
         D = obs_f.shape[1]
-        h1, h2 = [m.out_features for m in self.policy.pi if isinstance(m, nn.Linear)][:2]
-        rc = lib().pcc_ppo_minibatch_step(ptr(obs_f), ptr(act_f), ptr(logp_f), ptr(adv_f), ptr(ret_f), ptr(perm), start, count,
-                                          D, h1, h2, ptr(self.flat), ptr(self.adam_m), ptr(self.adam_v), max(self.adam_t, 1),
-                                          lr, 0.9, 0.999, self.adam_eps, self.clip, self.ent_coef, ptr(self.scratch),
-                                          ptr(grad_out), ptr(self.stats_buf),
+        h1, h2 = self.policy.hidden
+        rc = lib().pcc_ppo_minibatch_step(_ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), start, count,
+                                          D, h1, h2, _ptr(self.flat), _ptr(self.adam_m), _ptr(self.adam_v), max(self.adam_t, 1),
+                                          lr, 0.9, 0.999, self.adam_eps, self.clip, self.ent_coef, _ptr(self.scratch),
+                                          _ptr(grad_out), _ptr(self.stats_buf),
                                           ctypes.c_void_p(torch.cuda.current_stream(obs_f.device).cuda_stream))
         if rc != 0:
             raise RuntimeError("pcc_ppo_minibatch_step failed (%d)" % rc)

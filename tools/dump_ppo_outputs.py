@@ -1,14 +1,20 @@
 #!/usr/bin/env python3
-"""The fixed-shape PPO kernels' outputs on seeded inputs, straight through the C ABI of ONE build of the library, into a .pt
-file -- to compare two builds (GPU box):
+"""The PPO kernels' outputs on seeded inputs, one shape per kernel family, straight through the C ABI of ONE build of the
+library, into a .pt file -- to compare two builds (GPU box):
    python tools/dump_ppo_outputs.py path/libpcc_sim.so out.pt          for each build, then
    python tools/dump_ppo_outputs.py --compare a.pt b.pt                torch.equal on every tensor
-For (30; 32, 16) and (12; 32, 16): the gradient and statistics of a seeded minibatch (pcc_ppo_minibatch_step, lr = 0, with a
-permutation) and pcc_policy_act's four outputs.  Uses only symbols every build has."""
+For every shape of SHAPES: the gradient and statistics of a seeded minibatch (pcc_ppo_minibatch_step, lr = 0, with a
+permutation; 66 000 samples from row 7 on: ragged last tiles of both 32 and 64 samples, more tiles than workgroups) and
+pcc_policy_act's four outputs.  Uses only symbols every build has."""
 import ctypes, sys
 import torch
 
-SHAPES = [(30, 32, 16), (12, 32, 16)]
+SHAPES = [(30, 32, 16), (12, 32, 16),   # ppo_grad_mfma_kernel + policy_act_fixed_kernel
+          (36, 32, 16),                 # policy_act_fixed_kernel + the tiled gradient, DP 64
+          (30, 16, 8),                  # the generic policy_act_kernel + tiled DP 32
+          (45, 48, 24),                 # tiled 64 / (64, 32)
+          (120, 64, 64),                # tiled 128 / (64, 64)
+          (1, 1, 1)]                    # all padding
 
 
 def dump(path, out):

@@ -207,8 +207,8 @@ enum { PCC_TUNE_ROUND_PACKETS = 2, PCC_TUNE_TAKEOVER_LANES = 3,
        PCC_TUNE_RETIRE_GRID_FRAC = 22 /* retire launch: the grid is n / 16 workgroups plus this share of as many again (for envs of
                                     the 16-lane classes, 8 per workgroup); workgroups loop when there are more.  Default 0.125;
                                     1 = the worst case (twice n / 16: the dispatch of ~8 200 workgroups alone takes 0.1 ms) */,
-       PCC_TUNE_RESTART_FORK = 23 /* out of lockstep with shadows: the restart kernel (nearly always without work) beside the main
-                                    send launch on a side stream (1) or behind it on the caller's stream (0, default: measured faster) */,
+       PCC_TUNE_RESTART_FORK = 23 /* gone (out of lockstep with shadows: the restart kernel beside the main send launch on a side stream
+                                    instead of behind it, measured slower); only 0 is accepted */,
        PCC_TUNE_PARTS = 24 /* partitions of the batch (1 or 8): contiguous env-id ranges with work lists, item cursors and pool
                                     stacks of their own; workgroup b of a launch works for partition b % 8, i.e. an XCD keeps to
                                     one eighth of the rings (a scattered access costs 2.5x as much once the addresses an XCD
@@ -235,14 +235,12 @@ enum { PCC_TUNE_ROUND_PACKETS = 2, PCC_TUNE_TAKEOVER_LANES = 3,
                                     16) takes them anyway once it has waited this many naps; default 2 */,
        PCC_TUNE_FUSED_LIGHT_FRONT = 32 /* fused step: so many of the light-first workgroups per partition are dispatched in FRONT of the
                                     wave-path workgroups (a compute unit's memory pipeline serves its oldest wavefronts first); default 0 */,
-       PCC_TUNE_NOISE_SORTED = 33 /* USE_LATENCY_NOISE alone on one sender: 1 (default) = an interval is run by a wavefront per env as counts, two
+       PCC_TUNE_NOISE_SORTED = 33 /* USE_LATENCY_NOISE without the congestion window, one sender or two: 1 (default) = an interval is run by a wavefront per env as counts, two
                                     sorts and a scan (pcc-rl_amd/csrc/pcc_noise_sorted.hip) and the event loop takes only the envs whose events in
                                     flight do not fit its arrays; 2 = only its 256-event instance (the event loop takes the rest: what the
                                     tests use to cross the two); 0 = the event loop for every env.  Results do not depend on it. */,
-       PCC_TUNE_LIGHT_WGS = 34 /* send launch: light workgroups (4 wavefronts, an item each per round) per partition; their wavefronts take
-                                    further items when there are more items than wavefronts.  0 (default) = the worst case, an item per
-                                    wavefront.  32 = what stays resident next to 12 wave-path wavefronts per compute unit: measured no
-                                    faster (profiles/r06_knob_sweeps.json) */,
+       PCC_TUNE_LIGHT_WGS = 34 /* gone (send launch: only as many light workgroups per partition as stay resident, their wavefronts
+                                    taking further items; measured no faster, profiles/r06_knob_sweeps.json); only 0 is accepted */,
        PCC_TUNE_LIGHT_FRONT = 35 /* send launch: so many light workgroups per partition -- the ones with the longest lane-round items --
                                     are dispatched in FRONT of the wave-path workgroups (block order); the rest behind them as before.
                                     The launch ends with its longest lane-round items: in front they start ~5 us earlier (the
@@ -294,8 +292,8 @@ int pcc_set_cwnd_mode(pcc_sim_t *sim, int enable);
  * env's stream per hop (at a SEND it precedes the loss draw).  Packets overtake each other, so with the
  * option on an env keeps the reference's own structure -- a heap of each sender's events, ring_capacity
  * events per sender, allocated by this call (2 x 16 bytes x ring_capacity per sender) -- and one lane runs the
- * reference's event loop over it ("event-loop build"); there is no pcc_step_send / pcc_step_retire split.  With ONE sender and
- * no window the interval itself runs ahead of that launch without the event loop (PCC_TUNE_NOISE_SORTED,
+ * reference's event loop over it ("event-loop build"); there is no pcc_step_send / pcc_step_retire split.  Without the
+ * window (one sender or two) the interval itself runs ahead of that launch without the event loop (PCC_TUNE_NOISE_SORTED,
  * pcc-rl_amd/csrc/pcc_noise_sorted.hip: counts, two sorts and a scan by a workgroup per env; ~10x the event loop's speed).
  * Exact like the other paths either way (golden sets noise_*, two_sender_noise).  Uniforms: PCC_RNG_TRACE replays
  * the trace in draw order (three draws per packet); PCC_RNG_PHILOX numbers ALL draws of an interval

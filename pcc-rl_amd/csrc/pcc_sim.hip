@@ -5,6 +5,8 @@
 // What this replaces (reference = PCCproject/PCC-RL; "ns" = src/gym/network_sim.py, "so" =
 // src/common/sender_obs.py): SimulatedNetworkEnv.reset / step (ns:406-484) for N independent envs advanced one monitor
 // interval per step -- see pcc_dev.h for the formulation.
+#include <functional>
+
 #include "pcc_kernels.h"
 #include "pcc_policy.h"
 
@@ -42,7 +44,6 @@ struct pcc_sim {
     size_t tier_bytes[kMaxTiers];
     size_t ring_bytes;
     void *timeline_blob;
-    size_t timeline_bytes;
     bool ever_reset;
     bool lockstep;      // every env was last reset by the same full reset (host knows when `done` fires)
     uint32_t host_steps;
@@ -54,9 +55,8 @@ struct pcc_sim {
     size_t list_bytes;
     void *noise_blob;   // heap + RTT samples of the latency-noise option (allocated when it is switched on)
     void *noise_out_blob;  // ... and the per-env results of the heap-free interval (pcc_noise_sorted.hip)
-    uint32_t light_wgs; // PCC_TUNE_LIGHT_WGS: light workgroups per partition of the send launch (0 = what stays resident)
-    uint32_t light_front; // PCC_TUNE_LIGHT_FRONT: ... of which so many per partition are dispatched in front of the wave-path workgroups
-    int noise_sorted;   // PCC_TUNE_NOISE_SORTED: 1 = latency noise alone on one sender runs its intervals by sorting, 2 = only the small instance, 0 = the event loop
+    uint32_t light_front; // PCC_TUNE_LIGHT_FRONT: light workgroups of the send launch, per partition, dispatched in front of the wave-path workgroups
+    int noise_sorted;   // PCC_TUNE_NOISE_SORTED: 1 = latency noise without the window (one sender or two) runs its intervals by sorting, 2 = only the small instance, 0 = the event loop
     size_t noise_bytes;
     uint32_t ring_capacity;
     bool pools_pending;     // the pools of tiers >= 1 are not allocated yet (they are sized at the first reset, or by pcc_set_ring_pools)
@@ -66,8 +66,7 @@ struct pcc_sim {
     // side streams of the handle: the restart kernel (or, without shadows, the main send launch beside it) and the refill
     // kernel, forked from / joined to the caller's stream by events
     hipStream_t aux_wave, aux_restart;
-    hipEvent_t ev_fork, ev_wave, ev_restart;
-    int restart_fork;         // tuning: with shadows, the restart kernel beside the main send launch (side stream) or behind it
+    hipEvent_t ev_fork, ev_wave;
     double retire_grid_frac;  // tuning: share of the envs the retire grid expects in the wide classes (see launch_retire_half)
     uint32_t step_seq;      // sequence number of the last step (Dev::step_seq of its launches)
     void *shadow_blob;      // the shadows' private rings (allocated when envs first restart out of lockstep)
@@ -101,6 +100,12 @@ struct DeviceGuard {
         if (switched) (void)hipSetDevice(prev);
     }
 };
+
+// the streams and events a handle owns: created and destroyed over these lists
+std::vector<hipStream_t *> side_streams(pcc_sim *sim) { return {&sim->aux_wave, &sim->aux_restart}; }
+std::vector<hipEvent_t *> events(pcc_sim *sim) {
+    return {&sim->ev_fork, &sim->ev_wave, &sim->ev_ret, &sim->ev_refill[0], &sim->ev_refill[1], &sim->ev_refill[2], &sim->ev_refill[3]};
+}
 
 struct Carver {
     char *base;
@@ -145,6 +150,37 @@ int check_hip(hipError_t err, const char *what) {
     return fail(PCC_EHIP, "%s: %s", what, hipGetErrorString(err));
 }
 
+// Whether this handle's batch is stepped with work lists.  Small batches go without (items = the envs in index order): at
+// 4 096 envs of a few packets each the launch IS its chain of dependent loads, and the lists put three more in front
+// (counts -> list -> state)
+bool uses_lists(const pcc_sim_t *sim) { return sim->d.n >= (int64_t)sim->list_min_envs; }
+
+// Where one step writes: its observation, reward, done and step-record rows (any of them NULL)
+struct StepOut { float *obs, *reward; uint8_t *done; double *steps; };
+
+// ... and the rows of step t when those are the first rows of [T, ...] outputs
+StepOut row_of(const Dev &d, const StepOut &o, int t) {
+    const size_t row = (size_t)d.n * d.ns, k = (size_t)t;
+    return {o.obs ? o.obs + k * row * d.HF : nullptr, o.reward ? o.reward + k * row : nullptr, o.done ? o.done + k * (size_t)d.n : nullptr,
+            o.steps ? o.steps + k * row * PCC_STEP_COLS : nullptr};
+}
+
+// wave-path workgroups of a launch: persistent wavefronts, send_waves per compute unit, at most one wavefront per env, four
+// to a workgroup, every partition the same number
+int64_t wave_path_wgs(const pcc_sim_t *sim) {
+    const Dev &d = sim->d;
+    const int64_t P = d.parts;
+    int64_t waves = (int64_t)sim->cu_count * d.send_waves;
+    if (waves > d.n) waves = d.n;
+    return P * (((waves + 3) / 4 + P - 1) / P);
+}
+
+// grid of the kernels that walk a list of a few envs, a wavefront each (restart items, shadows to refill)
+unsigned few_envs_grid(const pcc_sim_t *sim) {
+    const int64_t wgs = (sim->d.n + 3) / 4;
+    return (unsigned)(sim->cu_count < wgs ? sim->cu_count : wgs);
+}
+
 // SEND half of one monitor interval: all envs (warm = 0) or the envs being reset (warm = 1).
 // With work lists (the lists the last retire launch filed, sim->read_buf): ONE launch of send_kernel holds the light
 // workgroups (the classes below the wave-path threshold, a lane per env) and the wave-path workgroups (the classes from the
@@ -155,73 +191,59 @@ int check_hip(hipError_t err, const char *what) {
 int launch_send(pcc_sim_t *sim, int warm, uint32_t warm_mi, int gate, const void *actions, int actions_f64, hipStream_t st) {
     const Dev &d = sim->d;
     const bool tr = d.rng_mode == PCC_RNG_TRACE;
-    // small batches go without work lists (items = the envs in index order): at 4 096 envs of a few packets each the
-    // launch IS its chain of dependent loads, and the lists put three more in front (counts -> list -> state)
-    const bool lists = sim->d.n >= (int64_t)sim->list_min_envs;
+    const bool lists = uses_lists(sim);
     const int read_buf = (warm || !lists) ? -1 : sim->read_buf;
     const int zero_buf = lists ? sim->fill_buf : -1;
+    // restart items can only be in lists that a retire launch with `restart` filed
+    const bool rs = read_buf >= 0 && sim->read_has_restarts;
     // light workgroups: one item per wavefront; the grid covers the worst case (every env light: n / E items + a partial
     // one per class), wavefronts without an item leave at once.  With lists every partition has its own share of the
     // workgroups (pcc_dev.h "partitions"): both kinds' counts are multiples of d.parts
-    const int64_t E = d.send_envs_per_wave;
-    if (read_buf < 0) {
-        const unsigned light_grid = (unsigned)(((d.n + E - 1) / E + 3) / 4);
-        pcc::launch_send(d, tr, light_grid, 0u, 0u, st, read_buf, zero_buf, warm, warm_mi, gate, actions, actions_f64);
-        return check_hip(hipGetLastError(), "send kernel launch");
+    const int64_t E = d.send_envs_per_wave, P = d.parts;
+    unsigned light_grid = (unsigned)(((d.n + E - 1) / E + 3) / 4), wave_grid = 0u, front = 0u;
+    if (read_buf >= 0) {
+        // (the classes from light_half_predict up go E / 2 envs to an item: the worst case is all of them)
+        const int64_t E_min = d.light_half_predict < 1e9f && E >= 2 ? E / 2 : E;
+        const int64_t light_items_part = ((int64_t)d.part_envs + E_min - 1) / E_min + kClasses;
+        // Light workgroups: an item per wavefront in the worst case.  (Round 6 measured the alternative -- only as many as stay
+        // resident next to the wave-path workgroups, their wavefronts taking a second item, the retired PCC_TUNE_LIGHT_WGS: the
+        // ones that wait for a slot start 40-60 us into the launch -- and it is no faster: 0.0974 against 0.0961 ms, settings
+        // alternating every step on one handle, profiles/r06_knob_sweeps.json.)
+        light_grid = (unsigned)(P * ((light_items_part + 3) / 4));
+        const bool wave = !d.use_cwnd && d.heavy_predict < 1e9;  // (USE_CWND sends every env lane-serially: no wave-path classes)
+        if (wave) wave_grid = (unsigned)wave_path_wgs(sim);
+        // PCC_TUNE_LIGHT_FRONT: the light workgroups with the longest items in front of the wave-path ones (block order = dispatch
+        // order): the launch ends with those items and the ~830 wave-path workgroups take the dispatcher ~5 us -- send launch
+        // 0.0893 -> 0.0864 ms at 6 per partition (tools/ab_block.py, three episodes a setting).  Not out of lockstep: measured slower
+        // there (0.132 -> 0.137-0.140 ms, bench.py --stagger)
+        if (wave && !rs) front = (unsigned)((int64_t)sim->light_front * P);
+        if (front > light_grid) front = light_grid / (unsigned)P * (unsigned)P;
     }
-    const int64_t P = d.parts;
-    // (the classes from light_half_predict up go E / 2 envs to an item: the worst case is all of them)
-    const int64_t E_min = d.light_half_predict < 1e9f && E >= 2 ? E / 2 : E;
-    const int64_t light_items_part = ((int64_t)d.part_envs + E_min - 1) / E_min + kClasses;
-    const unsigned worst_light_grid = (unsigned)(P * ((light_items_part + 3) / 4));
-    // restart items can only be in lists that a retire launch with `restart` filed
-    const bool rs = sim->read_has_restarts;
-    const bool wave = !d.use_cwnd && d.heavy_predict < 1e9;  // (USE_CWND sends every env lane-serially: no wave-path classes)
-    // wave-path workgroups: persistent wavefronts, send_waves per compute unit, at most one wavefront per env
-    int64_t waves = (int64_t)sim->cu_count * d.send_waves;
-    if (waves > d.n) waves = d.n;
-    const unsigned wave_grid = wave ? (unsigned)(P * (((waves + 3) / 4 + P - 1) / P)) : 0u;
-    // Light workgroups: an item per wavefront in the worst case.  (Round 6 measured the alternative -- only as many as stay
-    // resident next to the wave-path workgroups, their wavefronts taking a second item, PCC_TUNE_LIGHT_WGS: the ones that wait
-    // for a slot start 40-60 us into the launch -- and it is no faster: 0.0974 against 0.0961 ms, settings alternating every
-    // step on one handle, profiles/r06_knob_sweeps.json.)
-    unsigned light_grid = worst_light_grid;
-    if (wave && sim->light_wgs && (int64_t)sim->light_wgs * P < (int64_t)light_grid) light_grid = (unsigned)((int64_t)sim->light_wgs * P);
-    // PCC_TUNE_LIGHT_FRONT: the light workgroups with the longest items in front of the wave-path ones (block order = dispatch
-    // order): the launch ends with those items and the ~830 wave-path workgroups take the dispatcher ~5 us -- send launch
-    // 0.0893 -> 0.0864 ms at 6 per partition (tools/ab_block.py, three episodes a setting).  Not out of lockstep: measured slower
-    // there (0.132 -> 0.137-0.140 ms, bench.py --stagger)
-    unsigned front = (wave && !rs) ? (unsigned)((int64_t)sim->light_front * P) : 0u;
-    if (front > light_grid) front = light_grid / (unsigned)P * (unsigned)P;
-    const unsigned restart_grid = (unsigned)(sim->cu_count < (d.n + 3) / 4 ? sim->cu_count : (d.n + 3) / 4);
-    if (rs && d.shadows) {
+    auto main_launch = [&](hipStream_t s) {
+        pcc::launch_send(d, tr, light_grid, wave_grid, front, s, read_buf, zero_buf, warm, warm_mi, gate, actions, actions_f64);
+    };
+    if (!rs) {
+        main_launch(st);
+    } else if (d.shadows) {
         // with shadows nearly every restart is a swap inside the retire half: the restart list holds only the envs whose shadow
         // was not usable (a masked reset overtook it; links whose warm-up intervals overflow a shadow's rings) -- nearly always
-        // nobody: the kernel follows the main launch on the caller's stream, no fork, no join
-        if (sim->restart_fork) {   // ... or beside it on the side stream: it is done long before the main launch, so the join is free
-            if (hipEventRecord(sim->ev_fork, st) != hipSuccess) return fail(PCC_EHIP, "hipEventRecord failed");
-            (void)hipStreamWaitEvent(sim->aux_wave, sim->ev_fork, 0);
-            launch_send_restart(d, tr, restart_grid, sim->aux_wave, read_buf, actions, actions_f64);
-            (void)hipEventRecord(sim->ev_wave, sim->aux_wave);
-            pcc::launch_send(d, tr, light_grid, wave_grid, front, st, read_buf, zero_buf, warm, warm_mi, gate, actions, actions_f64);
-            (void)hipStreamWaitEvent(st, sim->ev_wave, 0);
-        } else {
-            pcc::launch_send(d, tr, light_grid, wave_grid, front, st, read_buf, zero_buf, warm, warm_mi, gate, actions, actions_f64);
-            launch_send_restart(d, tr, restart_grid < 32u ? restart_grid : 32u, st, read_buf, actions, actions_f64);  // (a handful of items at most)
-        }
-    } else if (rs) {
+        // nobody, a handful of items at most: the kernel follows the main launch on the caller's stream, no fork, no join.
+        // (Beside it on the side stream, the retired PCC_TUNE_RESTART_FORK, measured slower: bench --stagger 0.166 ms a step
+        // against 0.153.)
+        const unsigned restart_grid = few_envs_grid(sim);
+        main_launch(st);
+        launch_send_restart(d, tr, restart_grid < 32u ? restart_grid : 32u, st, read_buf, actions, actions_f64);
+    } else {
         // The restart items are a chain of dependent passes (reset, two warm-up intervals, the first interval): longer than
         // the whole main launch.  So the MAIN launch goes to the side stream and the restart kernel stays on the caller's:
         // what the next launch of the caller's stream waits for across streams has then long finished (a cross-stream
         // dependency on a kernel that is just ending costs ~15 us, one that ended long ago next to nothing)
         if (hipEventRecord(sim->ev_fork, st) != hipSuccess) return fail(PCC_EHIP, "hipEventRecord failed");
         (void)hipStreamWaitEvent(sim->aux_wave, sim->ev_fork, 0);
-        pcc::launch_send(d, tr, light_grid, wave_grid, front, sim->aux_wave, read_buf, zero_buf, warm, warm_mi, gate, actions, actions_f64);
+        main_launch(sim->aux_wave);
         (void)hipEventRecord(sim->ev_wave, sim->aux_wave);
-        launch_send_restart(d, tr, restart_grid, st, read_buf, actions, actions_f64);
+        launch_send_restart(d, tr, few_envs_grid(sim), st, read_buf, actions, actions_f64);
         (void)hipStreamWaitEvent(st, sim->ev_wave, 0);
-    } else {
-        pcc::launch_send(d, tr, light_grid, wave_grid, front, st, read_buf, zero_buf, warm, warm_mi, gate, actions, actions_f64);
     }
     if (rs && !warm) sim->restarts_pending = false;  // this launch runs what the restart list's envs were owed
     return check_hip(hipGetLastError(), "send kernel launch");
@@ -231,12 +253,12 @@ int launch_send(pcc_sim_t *sim, int warm, uint32_t warm_mi, int gate, const void
 // next send (buffer sim->fill_buf, cleared by the send launch before it)
 // restart: envs that finish their episode in this launch are reset inside it and filed in the restart list
 // pol: the policy epilogue (pcc_rollout): every env's next action from the observation row this launch writes
-int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm, int gate, int restart, float *obs_out,
-                       float *reward_out, uint8_t *done_out, double *steps_out, hipStream_t st, const PolicyArgs *pol = nullptr) {
+int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm, int gate, int restart, const StepOut &out,
+                       hipStream_t st, const PolicyArgs *pol = nullptr) {
     const Dev &d = sim->d;
     // workgroups: 8 envs each at 16 lanes per env, 16 at 8 lanes -- which envs go which way is decided on the device
     // (class counts), so the grid covers the worst case plus the one workgroup the split can leave partly filled
-    const bool lists = d.n >= (int64_t)sim->list_min_envs;
+    const bool lists = uses_lists(sim);
     const int read = (warm || !d.retire_sorted || !lists) ? -1 : sim->read_buf;  // the lists this step's send launch read
     // With lists the walk is n / 16 workgroups plus one more for every 16 envs of the wide classes (8 per workgroup there): the
     // grid is sized for retire_grid_frac of the envs being wide (default 1/8: about 3 % are) and the workgroups loop if there
@@ -247,7 +269,7 @@ int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm
     const int64_t narrow_part = ((int64_t)d.part_envs + kRetireEnvsPerBlockNarrow - 1) / kRetireEnvsPerBlockNarrow;
     const unsigned grid = (unsigned)(read >= 0 ? (int64_t)d.parts * (narrow_part + (int64_t)(sim->retire_grid_frac * (double)narrow_part) + 1) : narrow);
     const int fill = (warm || !lists) ? -1 : sim->fill_buf;
-    launch_retire(d, false, grid, st, read, fill, warm, warm_mi, last_warm, gate, restart, obs_out, reward_out, done_out, steps_out,
+    launch_retire(d, false, grid, st, read, fill, warm, warm_mi, last_warm, gate, restart, out.obs, out.reward, out.done, out.steps,
                   nullptr, 0, pol);
     const int rc = check_hip(hipGetLastError(), "retire kernel launch");
     if (rc == PCC_OK && !warm && lists) {
@@ -263,12 +285,11 @@ int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm
 // Both halves of a step as ONE launch (pcc_fused.hip) -- whenever the step is an ordinary one: work lists to read, no warm-up
 // interval, no restart list to serve or to fill (lockstep, or the caller resets), none of the engine options.  Returns
 // PCC_OK + *done = true when the step was launched; *done = false: the caller launches the two halves.
-int try_launch_fused(pcc_sim_t *sim, int restart, const void *actions, int actions_f64, float *obs_out, float *reward_out,
-                     uint8_t *done_out, double *steps_out, hipStream_t st, bool *done) {
+int try_launch_fused(pcc_sim_t *sim, int restart, const void *actions, int actions_f64, const StepOut &out, hipStream_t st, bool *done) {
     const Dev &d = sim->d;
     *done = false;
     if (!sim->fused || d.engine || d.use_cwnd || restart || sim->read_has_restarts || sim->restarts_pending) return PCC_OK;
-    if (d.n < (int64_t)sim->list_min_envs || sim->read_buf < 0 || !d.retire_sorted) return PCC_OK;
+    if (!uses_lists(sim) || sim->read_buf < 0 || !d.retire_sorted) return PCC_OK;
     if (d.q_cap == 0u) return PCC_OK;
     const bool tr = d.rng_mode == PCC_RNG_TRACE;
     int &blocks = sim->fused_blocks[tr ? 1 : 0];
@@ -282,10 +303,7 @@ int try_launch_fused(pcc_sim_t *sim, int restart, const void *actions, int actio
     if (cap < 2 * P) cap = 2 * P;
     if (light > cap / 2) light = cap / 2 / P * P;
     if (light < P) light = P;
-    const bool wave = d.heavy_predict < 1e9;
-    int64_t waves = (int64_t)sim->cu_count * d.send_waves;
-    if (waves > d.n) waves = d.n;
-    int64_t wave_wgs = wave ? P * (((waves + 3) / 4 + P - 1) / P) : 0;
+    int64_t wave_wgs = d.heavy_predict < 1e9 ? wave_path_wgs(sim) : 0;
     if (wave_wgs > cap - light) wave_wgs = cap - light;
     // (a small batch: no more workgroups than a wavefront per 8 envs and per light item need)
     int64_t light_need = P * (((int64_t)d.part_envs / (int64_t)(d.send_envs_per_wave ? d.send_envs_per_wave : 1) + kClasses + 3) / 4);
@@ -298,16 +316,16 @@ int try_launch_fused(pcc_sim_t *sim, int restart, const void *actions, int actio
     unsigned light_front = (unsigned)(P * (int64_t)sim->fused_light_front);
     if ((int64_t)light_front > grid - wave_wgs) light_front = (unsigned)((grid - wave_wgs) / P * P);
     if (sim->fused == 2) {   // experiment: the fused kernel's send part as the send launch, then the retire launch
-        launch_step_fused(d, tr, (unsigned)grid, (unsigned)wave_wgs, light_front, st, read, fill, fill, 0, actions, actions_f64, obs_out, reward_out, done_out,
-                          steps_out);
+        launch_step_fused(d, tr, (unsigned)grid, (unsigned)wave_wgs, light_front, st, read, fill, fill, 0, actions, actions_f64, out.obs, out.reward,
+                          out.done, out.steps);
         const int rc2 = check_hip(hipGetLastError(), "fused step kernel launch");
         if (rc2 != PCC_OK) return rc2;
         *done = true;
-        return launch_retire_half(sim, 0, 0, 0, 0, 0, obs_out, reward_out, done_out, steps_out, st);
+        return launch_retire_half(sim, 0, 0, 0, 0, 0, out, st);
     }
     if (sim->clean_buf != fill) launch_clear_list_buffer(d, st, fill);
-    launch_step_fused(d, tr, (unsigned)grid, (unsigned)wave_wgs, light_front, st, read, fill, zero, 1, actions, actions_f64, obs_out, reward_out, done_out,
-                      steps_out);
+    launch_step_fused(d, tr, (unsigned)grid, (unsigned)wave_wgs, light_front, st, read, fill, zero, 1, actions, actions_f64, out.obs, out.reward,
+                      out.done, out.steps);
     const int rc = check_hip(hipGetLastError(), "fused step kernel launch");
     if (rc != PCC_OK) return rc;
     sim->read_buf = fill;
@@ -319,12 +337,14 @@ int try_launch_fused(pcc_sim_t *sim, int restart, const void *actions, int actio
     return PCC_OK;
 }
 
+// One monitor interval of a batch that is not a small one.  pol (pcc_rollout's epilogue path): the policy in the retire
+// launch's epilogue -- the send and the retire launch then, never the one-launch step.
 int launch_mi(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm, int gate, int restart, const void *actions,
-              int actions_f64, float *obs_out, float *reward_out, uint8_t *done_out, double *steps_out, hipStream_t st) {
+              int actions_f64, const StepOut &out, hipStream_t st, const PolicyArgs *pol = nullptr) {
     if (sim->d.engine) {
         // the event-loop build (latency noise; the congestion window with two senders): the whole interval is one launch of
         // the retire kernel's NOISE build (no send half, no work lists)
-        // Latency noise alone on one sender: the interval itself is run ahead of that launch, a wavefront per env, without
+        // Latency noise without the window (one sender or two): the interval itself is run ahead of that launch, a wavefront per env, without
         // the event loop (pcc_noise_sorted.hip); the retire launch picks the results up env by env (NoiseOut::seq) and
         // runs the event loop for the envs that were left alone.
         sim->d.noise_seq++;
@@ -333,18 +353,18 @@ int launch_mi(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm, int gat
         if (!sorted) d.noise_out = nullptr;
         else launch_noise_sorted(d, st, warm, warm_mi, gate, actions, actions_f64, sim->noise_sorted == 2);
         const unsigned grid = (unsigned)((d.n + kRetireEnvsPerBlockNarrow - 1) / kRetireEnvsPerBlockNarrow);
-        launch_retire(d, true, grid, st, -1, -1, warm, warm_mi, last_warm, gate, 0, obs_out, reward_out, done_out, steps_out,
+        launch_retire(d, true, grid, st, -1, -1, warm, warm_mi, last_warm, gate, 0, out.obs, out.reward, out.done, out.steps,
                       actions, actions_f64);
         return check_hip(hipGetLastError(), "event-loop kernel launch");
     }
-    if (!warm && !gate) {
+    if (!warm && !gate && !pol) {
         bool done = false;
-        const int rf = try_launch_fused(sim, restart, actions, actions_f64, obs_out, reward_out, done_out, steps_out, st, &done);
+        const int rf = try_launch_fused(sim, restart, actions, actions_f64, out, st, &done);
         if (rf != PCC_OK || done) return rf;
     }
     const int rc = launch_send(sim, warm, warm_mi, gate, actions, actions_f64, st);
     if (rc != PCC_OK) return rc;
-    return launch_retire_half(sim, warm, warm_mi, last_warm, gate, restart, obs_out, reward_out, done_out, steps_out, st);
+    return launch_retire_half(sim, warm, warm_mi, last_warm, gate, restart, out, st, pol);
 }
 
 // reset(): parameters + state, then the two unrecorded warm-up MIs (ns:469-484).  gate: the launches
@@ -357,7 +377,7 @@ int launch_reset(pcc_sim_t *sim, const uint8_t *mask, int use_done, int gate, fl
     launch_reset_init(d, st, mask, use_done, gate, all_envs, obs_out);
     int rc = check_hip(hipGetLastError(), "reset kernel launch");
     for (uint32_t w = 0; w < 2 && rc == PCC_OK; w++)
-        rc = launch_mi(sim, 1, w, w == 1, gate, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, st);
+        rc = launch_mi(sim, 1, w, w == 1, gate, 0, nullptr, 0, StepOut{}, st);
     return rc;
 }
 
@@ -366,7 +386,7 @@ int launch_reset(pcc_sim_t *sim, const uint8_t *mask, int use_done, int gate, fl
 // send half can take such items: not with the congestion-window option (no wave path) or the latency-noise
 // option (no send half) -- those keep the gated reset launches after the step.
 bool restarts_in_step(const pcc_sim_t *sim, int auto_reset) {
-    return auto_reset && !sim->lockstep && !sim->d.use_cwnd && !sim->d.engine && sim->d.n >= (int64_t)sim->list_min_envs;
+    return auto_reset && !sim->lockstep && !sim->d.use_cwnd && !sim->d.engine && uses_lists(sim);
 }
 
 // Shadows (the next episode of an env prepared ahead of time, swapped in when it finishes: pcc_dev.h, pcc_send_restart.hip)
@@ -455,7 +475,168 @@ void set_parts(pcc_sim_t *sim, uint32_t parts) {
     d.part_envs = (uint32_t)((per + 63) / 64 * 64);
 }
 
+// The pools of tiers 1, 2, 3 with a slot for one sender in div[c] (tier 0 is a slot per sender), their free stacks full.
+int alloc_pools(pcc_sim_t *sim, const unsigned *div) {
+    Dev &d = sim->d;
+    for (int c = 1; c < d.n_tiers; c++) {
+        const int rc = alloc_tier(sim, c, div[c]);
+        if (rc != PCC_OK) return rc;
+    }
+    sim->pools_pending = false;
+    return init_pool_stacks(sim);
+}
+
+// Default pool sizes, at the handle's first reset.  A sender keeps the slots it was promoted into until its env is reset, so
+// the pools of tiers 1, 2, 3 can never run dry when each has a slot for every sender (divisor 1) -- and a policy that climbs
+// towards the rate limit on every link (what PPO learns on generous links) does need most of that.  An MI355X has 288 GB: the
+// pools get what a third of the memory that is free right now pays for, the largest tier halved first (round 3 sized them
+// for U(-1, 1) policies -- divisors 2, 8, 32, measured need ~25 %, ~2 %, ~0.02 % of the senders -- and a saturating policy
+// ended a training run with PCC_FLAG_POOL_EXHAUSTED); those divisors are the floor.  pcc_set_ring_pools overrides.
+int ensure_pools(pcc_sim_t *sim) {
+    if (!sim->pools_pending) return PCC_OK;
+    Dev &d = sim->d;
+    unsigned div[kMaxTiers] = {1, 1, 1, 1};
+    const unsigned floor_div[kMaxTiers] = {1, 2, 8, 32};
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
+    const double budget = 0.33 * (double)free_b;
+    const double senders = (double)d.n * d.ns;
+    auto tier_bytes = [&](int c) { return senders / div[c] * 3.0 * (double)((size_t)d.cap0 << (2 * c)) * sizeof(double2); };
+    for (;;) {
+        double total = 0.0;
+        int big = -1;
+        for (int c = 1; c < d.n_tiers; c++) {
+            total += tier_bytes(c);
+            if (div[c] < floor_div[c] && (big < 0 || tier_bytes(c) > tier_bytes(big))) big = c;
+        }
+        if (total <= budget || big < 0) break;
+        div[big] *= 2;
+    }
+    return alloc_pools(sim, div);
+}
+
+// The work lists are dropped: the next step walks the envs in index order, and no list buffer is known to be clean.
+void drop_lists(pcc_sim_t *sim) { sim->read_buf = sim->clean_buf = -1; }
+
+// What the envs hold no longer fits the handle (other rings, other partitions, another engine): nothing steps before a full
+// pcc_reset -- which starts everything over, the restart list included.
+void need_full_reset(pcc_sim_t *sim) {
+    sim->ever_reset = false;
+    sim->restarts_pending = false;
+    drop_lists(sim);
+}
+
+// Every sender back into its own tier-0 rings and the pools' free stacks rebuilt for `parts` partitions -- of the pools as
+// they are (div = NULL; pools that do not exist yet get their stacks with them) or of new ones with a slot for one sender in
+// div[c].  Synchronizes the device; whatever was in flight is dropped: a full reset must follow.
+int rebuild_pools(pcc_sim_t *sim, uint32_t parts, const unsigned *div) {
+    DeviceGuard guard(sim->device);
+    if (hipDeviceSynchronize() != hipSuccess) return fail(PCC_EHIP, "hipDeviceSynchronize failed");
+    set_parts(sim, parts);
+    const int rc = div ? alloc_pools(sim, div) : sim->pools_pending ? PCC_OK : init_pool_stacks(sim);
+    if (rc != PCC_OK) return rc;
+    launch_forget_ring_slots(sim->d, nullptr);
+    if (hipDeviceSynchronize() != hipSuccess) return fail(PCC_EHIP, "forget_ring_slots_kernel failed");
+    need_full_reset(sim);
+    return PCC_OK;
+}
+
 }  // namespace
+
+// pcc_set_tuning's table: one row per key -- what is accepted, how the value is stored, where.  The rules are pure (key,
+// value -> code, stored value: pcc::tuning_value, which tests/models/tuning_model.cpp runs without a device).
+namespace {
+
+enum TuneRule {
+    kTrunc,    // lo <= value <= hi, truncated to an integer
+    kRound4,   // ... and rounded up to a multiple of 4
+    kInteger,  // lo <= value <= hi and an integer
+    kEnds,     // lo or hi, nothing else (lo = hi = 0: a retired key)
+    kReal,     // lo <= value <= hi, as it is
+    kReal32,   // ... as a float, 1e9 standing for everything above
+    kAny,      // any value, as it is
+    kFlag,     // any value: 0 stays 0, everything else is 1
+    kSat       // any value: truncated into 0 .. 0xFFFFFFFF, the latter from hi up
+};
+
+struct TuneKey {
+    int key;
+    const char *name;
+    TuneRule rule;
+    double lo, hi;
+    void (*set)(pcc_sim &, double);   // (NULL: nothing to store, or pcc_set_tuning stores it itself)
+};
+
+#define PCC_SET(field) [](pcc_sim &s, double v) { s.field = static_cast<decltype(s.field)>(v); }
+constexpr double kInf = HUGE_VAL;
+const TuneKey kTune[] = {
+    {PCC_TUNE_ROUND_PACKETS, "round_packets", kRound4, 4, 1048576, PCC_SET(d.round_packets)},
+    {PCC_TUNE_TAKEOVER_LANES, "takeover_lanes", kTrunc, 0, 64, PCC_SET(d.takeover_lanes)},
+    {PCC_TUNE_SEND_ENVS_PER_WAVE, "send_envs_per_wave", kTrunc, 1, 64, PCC_SET(d.send_envs_per_wave)},
+    {PCC_TUNE_HEAVY_PREDICT, "heavy_predict", kAny, 0, 0, PCC_SET(d.heavy_predict)},
+    {PCC_TUNE_SEND_WAVES, "send_waves", kTrunc, 1, 32, PCC_SET(d.send_waves)},
+    {PCC_TUNE_TEAM_PREDICT, "team_predict", kAny, 0, 0, PCC_SET(d.team_predict)},
+    {PCC_TUNE_HEAVY_ITEM_PACKETS, "heavy_item_packets", kReal32, 0, 1e9, PCC_SET(d.heavy_item_packets)},
+    {PCC_TUNE_RETIRE_WIDE_PREDICT, "retire_wide_predict", kReal32, 0, kInf, PCC_SET(d.retire_wide_predict)},
+    {PCC_TUNE_LIST_MIN_ENVS, "list_min_envs", kTrunc, 0, 4e9, nullptr},
+    {PCC_TUNE_RETIRE_SORTED, "retire_sorted", kFlag, 0, 0, PCC_SET(d.retire_sorted)},
+    {PCC_TUNE_LIGHT_SNAKE, "light_snake", kFlag, 0, 0, PCC_SET(d.light_snake)},
+    {PCC_TUNE_WAVE_OLDEST_FIRST, "wave_oldest_first", kFlag, 0, 0, PCC_SET(d.wave_oldest_first)},
+    {PCC_TUNE_PRIO_LEVEL, "prio_level", kTrunc, 0, 3, PCC_SET(d.prio_level)},
+    {PCC_TUNE_PRIO_LIGHT_ITEMS, "prio_light_items", kSat, 0, 4e9, PCC_SET(d.prio_light_items)},
+    {PCC_TUNE_PRIO_WAVE_ITEMS, "prio_wave_items", kSat, 0, 4e9, PCC_SET(d.prio_wave_items)},
+    {PCC_TUNE_PRIO_TEAM, "prio_team", kFlag, 0, 0, PCC_SET(d.prio_team)},
+    // retired experiments, each measured no faster than what stayed (profiles/r04_experiments.json; LIGHT_WGS, RESTART_FORK:
+    // the figures are in launch_send)
+    {PCC_TUNE_SPLIT_STREAMS, "split_streams", kEnds, 0, 0, nullptr},
+    {PCC_TUNE_LIGHT_FRONT_WGS, "light_front_wgs", kEnds, 0, 0, nullptr},
+    {PCC_TUNE_RESTART_FORK, "restart_fork", kEnds, 0, 0, nullptr},
+    {PCC_TUNE_LIGHT_WGS, "light_wgs", kEnds, 0, 0, nullptr},
+    {PCC_TUNE_RETIRE_GRID_FRAC, "retire_grid_frac", kReal, 0, 1, PCC_SET(retire_grid_frac)},
+    {PCC_TUNE_PARTS, "parts", kEnds, 1, (double)kParts, nullptr},
+    {PCC_TUNE_LIGHT_HALF_PREDICT, "light_half_predict", kReal32, 0, kInf, PCC_SET(d.light_half_predict)},
+    {PCC_TUNE_FUSED, "fused", kAny, 0, 0, nullptr},
+    {PCC_TUNE_FUSED_ACQUIRE, "fused_acquire", kEnds, 0, 2, PCC_SET(d.fused_acquire)},
+    {PCC_TUNE_FUSED_LIGHT_WGS, "fused_light_wgs", kTrunc, 1, 4096, PCC_SET(fused_light_wgs)},
+    {PCC_TUNE_FUSED_MAX_NAPS, "fused_max_naps", kTrunc, 1, 1024, PCC_SET(d.fused_max_naps)},
+    {PCC_TUNE_FUSED_PARTIAL_NAPS, "fused_partial_naps", kTrunc, 0, 1e6, PCC_SET(d.fused_partial_naps)},
+    {PCC_TUNE_FUSED_DEBUG, "fused_debug", kSat, 0, 4294967295.0, PCC_SET(d.fused_debug)},
+    {PCC_TUNE_FUSED_LIGHT_FRONT, "fused_light_front", kTrunc, 0, 4096, PCC_SET(fused_light_front)},
+    {PCC_TUNE_NOISE_SORTED, "noise_sorted", kInteger, 0, 2, PCC_SET(noise_sorted)},
+    {PCC_TUNE_LIGHT_FRONT, "light_front", kTrunc, 0, 65536, PCC_SET(light_front)},
+    {PCC_TUNE_ROLLOUT_EPILOGUE, "rollout_epilogue", kInteger, 0, 1, PCC_SET(rollout_epilogue)},
+};
+#undef PCC_SET
+
+}  // namespace
+
+namespace pcc {
+// What pcc_set_tuning makes of (key, value): PCC_OK and the value as it is stored, or PCC_EINVAL and the message.
+int tuning_value(int key, double value, double *stored) {
+    const TuneKey *k = nullptr;
+    for (const TuneKey &row : kTune)
+        if (row.key == key) k = &row;
+    if (!k) return fail(PCC_EINVAL, "unknown tuning key %d", key);
+    double v = value;
+    switch (k->rule) {
+        case kAny: break;
+        case kFlag: v = value != 0.0 ? 1.0 : 0.0; break;
+        case kSat: v = value >= k->hi ? 4294967295.0 : value > 0.0 ? trunc(value) : 0.0; break;   // (NaN: 0)
+        case kEnds:
+            if (value == k->lo || value == k->hi) break;
+            if (k->hi == 0.0) return fail(PCC_EINVAL, "%s (tuning key %d) was an experiment that measured no faster and is gone (only 0 is accepted)", k->name, key);
+            return fail(PCC_EINVAL, "%s must be %g or %g", k->name, k->lo, k->hi);
+        default:
+            if (!(value >= k->lo && value <= k->hi) || (k->rule == kInteger && value != trunc(value)))
+                return fail(PCC_EINVAL, "%s out of range: it must be %s in [%g, %g]", k->name, k->rule == kInteger ? "an integer" : "a value", k->lo, k->hi);
+            if (k->rule == kTrunc) v = trunc(value);
+            if (k->rule == kRound4) v = (double)(((uint32_t)value + 3u) & ~3u);
+            if (k->rule == kReal32) v = (double)(value >= 1e9 ? 1e9f : (float)value);
+    }
+    *stored = v;
+    return PCC_OK;
+}
+}  // namespace pcc
 
 extern "C" {
 
@@ -562,9 +743,8 @@ int pcc_create(int64_t n_envs, int n_senders, int history_len, const int32_t *fe
         return fail(PCC_EHIP, "initialising the env state failed");
     }
     if (kProfile && getenv("PCC_DEBUG_TIMELINE") && atoi(getenv("PCC_DEBUG_TIMELINE"))) {  // profile build only
-        sim->timeline_bytes = (size_t)n_envs * 4 * 8 * sizeof(uint64_t);
-        if (hipMalloc(&sim->timeline_blob, sim->timeline_bytes) != hipSuccess ||
-            hipMemset(sim->timeline_blob, 0, sim->timeline_bytes) != hipSuccess) {
+        const size_t timeline_bytes = (size_t)n_envs * 4 * 8 * sizeof(uint64_t);
+        if (hipMalloc(&sim->timeline_blob, timeline_bytes) != hipSuccess || hipMemset(sim->timeline_blob, 0, timeline_bytes) != hipSuccess) {
             pcc_destroy(sim);
             return fail(PCC_ENOMEM, "hipMalloc for the debug timeline failed");
         }
@@ -595,17 +775,10 @@ int pcc_create(int64_t n_envs, int n_senders, int history_len, const int32_t *fe
     sim->list_min_envs = 8192;
     sim->cu_count = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
     sim->retire_grid_frac = 0.125;
-    sim->restart_fork = 0;   // (measured, bench --stagger: behind the main launch 0.153 ms, beside it 0.166)
-    if (hipStreamCreateWithFlags(&sim->aux_wave, hipStreamNonBlocking) != hipSuccess ||
-        hipStreamCreateWithFlags(&sim->aux_restart, hipStreamNonBlocking) != hipSuccess ||
-        hipEventCreateWithFlags(&sim->ev_fork, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sim->ev_wave, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sim->ev_restart, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sim->ev_ret, hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sim->ev_refill[0], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sim->ev_refill[1], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sim->ev_refill[2], hipEventDisableTiming) != hipSuccess ||
-        hipEventCreateWithFlags(&sim->ev_refill[3], hipEventDisableTiming) != hipSuccess) {
+    bool made = true;
+    for (hipStream_t *q : side_streams(sim)) made = made && hipStreamCreateWithFlags(q, hipStreamNonBlocking) == hipSuccess;
+    for (hipEvent_t *e : events(sim)) made = made && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
+    if (!made) {
         pcc_destroy(sim);
         return fail(PCC_EHIP, "creating the side streams of the send half failed");
     }
@@ -652,14 +825,10 @@ void pcc_destroy(pcc_sim_t *sim) {
     if (!sim) return;
     DeviceGuard guard(sim->device);
     // (the side streams' work is always joined to the caller's stream before a call returns; drain them before they go)
-    if (sim->aux_wave) { (void)hipStreamSynchronize(sim->aux_wave); (void)hipStreamDestroy(sim->aux_wave); }
-    if (sim->aux_restart) { (void)hipStreamSynchronize(sim->aux_restart); (void)hipStreamDestroy(sim->aux_restart); }
-    if (sim->ev_fork) (void)hipEventDestroy(sim->ev_fork);
-    if (sim->ev_wave) (void)hipEventDestroy(sim->ev_wave);
-    if (sim->ev_restart) (void)hipEventDestroy(sim->ev_restart);
-    if (sim->ev_ret) (void)hipEventDestroy(sim->ev_ret);
-    for (int k = 0; k < 4; k++)
-        if (sim->ev_refill[k]) (void)hipEventDestroy(sim->ev_refill[k]);
+    for (hipStream_t *q : side_streams(sim))
+        if (*q) { (void)hipStreamSynchronize(*q); (void)hipStreamDestroy(*q); }
+    for (hipEvent_t *e : events(sim))
+        if (*e) (void)hipEventDestroy(*e);
     if (sim->shadow_blob) (void)hipFree(sim->shadow_blob);
     if (sim->timeline_blob) (void)hipFree(sim->timeline_blob);
     if (sim->list_blob) (void)hipFree(sim->list_blob);
@@ -743,103 +912,25 @@ int pcc_set_seed(pcc_sim_t *sim, uint64_t seed) {
 
 int pcc_set_tuning(pcc_sim_t *sim, int key, double value) {
     if (!sim) return fail(PCC_EINVAL, "sim is NULL");
-    switch (key) {
-        case PCC_TUNE_ROUND_PACKETS:
-            if (value < 4 || value > 1048576) return fail(PCC_EINVAL, "round_packets out of range");
-            sim->d.round_packets = ((uint32_t)value + 3u) & ~3u;
-            return PCC_OK;
-        case PCC_TUNE_SEND_ENVS_PER_WAVE:
-            if (value < 1 || value > 64) return fail(PCC_EINVAL, "send_envs_per_wave out of range");
-            sim->d.send_envs_per_wave = (uint32_t)value;
-            return PCC_OK;
-        case PCC_TUNE_HEAVY_PREDICT: sim->d.heavy_predict = value; return PCC_OK;
-        case PCC_TUNE_TEAM_PREDICT: sim->d.team_predict = value; return PCC_OK;
+    double v = 0.0;
+    const int rc = pcc::tuning_value(key, value, &v);
+    if (rc != PCC_OK) return rc;
+    switch (key) {   // the keys that do more than store a value
         case PCC_TUNE_LIST_MIN_ENVS: {
-            if (!(value >= 0.0 && value <= 4e9)) return fail(PCC_EINVAL, "list_min_envs out of range");
             if (sim->send_pending) return fail(PCC_ESTATE, "pcc_set_tuning(LIST_MIN_ENVS) between pcc_step_send and pcc_step_retire");
             // the lists are about to be dropped: what is still owed to the envs of the restart list (new links, warm-up
             // intervals) is done first, on the stream the caller last stepped on
             DeviceGuard guard(sim->device);
-            const int rc = flush_restarts(sim, sim->last_stream);
-            if (rc != PCC_OK) return rc;
-            sim->list_min_envs = (uint32_t)value;
-            sim->clean_buf = -1;
-            sim->read_buf = -1;  // (whatever was filed is dropped: the next step walks the envs in index order)
+            const int rf = flush_restarts(sim, sim->last_stream);
+            if (rf != PCC_OK) return rf;
+            sim->list_min_envs = (uint32_t)v;
+            drop_lists(sim);
             return PCC_OK;
         }
-        case PCC_TUNE_RETIRE_SORTED: sim->d.retire_sorted = value != 0.0 ? 1u : 0u; return PCC_OK;
-        case PCC_TUNE_LIGHT_SNAKE: sim->d.light_snake = value != 0.0 ? 1u : 0u; return PCC_OK;
-        case PCC_TUNE_WAVE_OLDEST_FIRST: sim->d.wave_oldest_first = value != 0.0 ? 1u : 0u; return PCC_OK;
-        case PCC_TUNE_PRIO_LEVEL:
-            if (!(value >= 0.0 && value <= 3.0)) return fail(PCC_EINVAL, "prio_level must be 0..3");
-            sim->d.prio_level = (uint32_t)value;
-            return PCC_OK;
-        case PCC_TUNE_PRIO_LIGHT_ITEMS: sim->d.prio_light_items = value >= 4e9 ? 0xFFFFFFFFu : (uint32_t)(value < 0.0 ? 0.0 : value); return PCC_OK;
-        case PCC_TUNE_PRIO_WAVE_ITEMS: sim->d.prio_wave_items = value >= 4e9 ? 0xFFFFFFFFu : (uint32_t)(value < 0.0 ? 0.0 : value); return PCC_OK;
-        case PCC_TUNE_PRIO_TEAM: sim->d.prio_team = value != 0.0 ? 1u : 0u; return PCC_OK;
-        case PCC_TUNE_RESTART_FORK: sim->restart_fork = value != 0.0 ? 1 : 0; return PCC_OK;
-        case PCC_TUNE_RETIRE_GRID_FRAC:
-            if (!(value >= 0.0 && value <= 1.0)) return fail(PCC_EINVAL, "retire_grid_frac must be in [0, 1]");
-            sim->retire_grid_frac = value;
-            return PCC_OK;
-        case PCC_TUNE_LIGHT_FRONT_WGS:   // (round 4 experiments; measured slower and removed: profiles/r04_experiments.json)
-        case PCC_TUNE_SPLIT_STREAMS:
-            if (value != 0.0) return fail(PCC_EINVAL, "tuning key %d was an experiment of round 4 and is gone (only 0 is accepted)", key);
-            return PCC_OK;
-        case PCC_TUNE_LIGHT_HALF_PREDICT:
-            if (!(value >= 0.0)) return fail(PCC_EINVAL, "light_half_predict out of range");
-            sim->d.light_half_predict = value >= 1e9 ? 1e9f : (float)value;
-            return PCC_OK;
-        case PCC_TUNE_PARTS: {
-            if (value != 1.0 && value != (double)kParts) return fail(PCC_EINVAL, "parts must be 1 or %u", kParts);
+        case PCC_TUNE_PARTS:
             if (sim->send_pending) return fail(PCC_ESTATE, "pcc_set_tuning(PARTS) between pcc_step_send and pcc_step_retire");
-            if ((uint32_t)value == sim->d.parts) return PCC_OK;
-            // the pool stacks are per partition: everybody back into tier 0, the stacks rebuilt -- a reset must follow
-            DeviceGuard guard(sim->device);
-            if (hipDeviceSynchronize() != hipSuccess) return fail(PCC_EHIP, "hipDeviceSynchronize failed");
-            set_parts(sim, (uint32_t)value);
-            const int rc = sim->pools_pending ? PCC_OK : init_pool_stacks(sim);   // (pools that do not exist yet get their stacks with them)
-            if (rc != PCC_OK) return rc;
-            launch_forget_ring_slots(sim->d, nullptr);
-            if (hipDeviceSynchronize() != hipSuccess) return fail(PCC_EHIP, "forget_ring_slots_kernel failed");
-            sim->ever_reset = false;
-            sim->restarts_pending = false;
-            sim->read_buf = -1;
-            sim->clean_buf = -1;   // (the views of the list buffers moved)
-            return PCC_OK;
-        }
-        case PCC_TUNE_RETIRE_WIDE_PREDICT:
-            if (!(value >= 0.0)) return fail(PCC_EINVAL, "retire_wide_predict out of range");
-            sim->d.retire_wide_predict = value >= 1e9 ? 1e9f : (float)value;
-            return PCC_OK;
-        case PCC_TUNE_LIGHT_WGS:
-            if (!(value >= 0.0 && value <= 65536.0)) return fail(PCC_EINVAL, "light_wgs out of range");
-            sim->light_wgs = (uint32_t)value;
-            return PCC_OK;
-        case PCC_TUNE_LIGHT_FRONT:
-            if (!(value >= 0.0 && value <= 65536.0)) return fail(PCC_EINVAL, "light_front out of range");
-            sim->light_front = (uint32_t)value;
-            return PCC_OK;
-        case PCC_TUNE_ROLLOUT_EPILOGUE:
-            if (value != 0.0 && value != 1.0) return fail(PCC_EINVAL, "rollout_epilogue must be 0 or 1");
-            sim->rollout_epilogue = (int)value;
-            return PCC_OK;
-        case PCC_TUNE_NOISE_SORTED:
-            if (value != 0.0 && value != 1.0 && value != 2.0) return fail(PCC_EINVAL, "noise_sorted must be 0, 1 or 2");
-            sim->noise_sorted = (int)value;
-            return PCC_OK;
-        case PCC_TUNE_HEAVY_ITEM_PACKETS:
-            if (!(value >= 0.0 && value <= 1e9)) return fail(PCC_EINVAL, "heavy_item_packets out of range");
-            sim->d.heavy_item_packets = (float)value;
-            return PCC_OK;
-        case PCC_TUNE_SEND_WAVES:
-            if (!(value >= 1.0 && value <= 32.0)) return fail(PCC_EINVAL, "send_waves out of range");
-            sim->d.send_waves = (uint32_t)value;
-            return PCC_OK;
-        case PCC_TUNE_TAKEOVER_LANES:
-            if (value < 0 || value > 64) return fail(PCC_EINVAL, "takeover_lanes out of range");
-            sim->d.takeover_lanes = (uint32_t)value;
-            return PCC_OK;
+            if ((uint32_t)v == sim->d.parts) return PCC_OK;
+            return rebuild_pools(sim, (uint32_t)v, nullptr);   // (the pool stacks and the views of the list buffers are per partition)
         case PCC_TUNE_FUSED:
             // experimental: its hand-off inside a launch counts on what was validated on one configuration
             // only -- a gfx950 with 8 XCDs in one partition (XCC_ID & 7 names the L2 a wavefront shares with its consumers)
@@ -848,72 +939,12 @@ int pcc_set_tuning(pcc_sim_t *sim, int key, double value) {
                 return fail(PCC_EINVAL, "the one-launch step is validated for a device of %u XCDs in one partition; this one reports %d", kXcds, sim->xcc_count);
             sim->fused = value == 2.0 ? 2 : (value != 0.0 ? 1 : 0);
             return PCC_OK;
-        case PCC_TUNE_FUSED_ACQUIRE:
-            if (value != 0.0 && value != 2.0) return fail(PCC_EINVAL, "fused_acquire must be 0 or 2");
-            sim->d.fused_acquire = (uint32_t)value;
+        default:
+            for (const TuneKey &k : kTune)
+                if (k.key == key && k.set) k.set(*sim, v);
             return PCC_OK;
-        case PCC_TUNE_FUSED_LIGHT_FRONT:
-            if (!(value >= 0.0 && value <= 4096.0)) return fail(PCC_EINVAL, "fused_light_front out of range");
-            sim->fused_light_front = (uint32_t)value;
-            return PCC_OK;
-        case PCC_TUNE_FUSED_DEBUG: sim->d.fused_debug = (uint32_t)value; return PCC_OK;
-        case PCC_TUNE_FUSED_PARTIAL_NAPS:
-            if (!(value >= 0.0 && value <= 1e6)) return fail(PCC_EINVAL, "fused_partial_naps out of range");
-            sim->d.fused_partial_naps = (uint32_t)value;
-            return PCC_OK;
-        case PCC_TUNE_FUSED_MAX_NAPS:
-            if (!(value >= 1.0 && value <= 1024.0)) return fail(PCC_EINVAL, "fused_max_naps out of range");
-            sim->d.fused_max_naps = (uint32_t)value;
-            return PCC_OK;
-        case PCC_TUNE_FUSED_LIGHT_WGS:
-            if (!(value >= 1.0 && value <= 4096.0)) return fail(PCC_EINVAL, "fused_light_wgs out of range");
-            sim->fused_light_wgs = (uint32_t)value;
-            return PCC_OK;
-        default: return fail(PCC_EINVAL, "unknown tuning key %d", key);
     }
 }
-
-namespace {
-// The pools of tiers 1, 2, 3 with a slot for one sender in div[c] (tier 0 is a slot per sender), their free stacks full.
-int alloc_pools(pcc_sim_t *sim, const unsigned (&div)[kMaxTiers]) {
-    Dev &d = sim->d;
-    for (int c = 1; c < d.n_tiers; c++) {
-        const int rc = alloc_tier(sim, c, div[c]);
-        if (rc != PCC_OK) return rc;
-    }
-    sim->pools_pending = false;
-    return init_pool_stacks(sim);
-}
-
-// Default pool sizes, at the handle's first reset.  A sender keeps the slots it was promoted into until its env is reset, so
-// the pools of tiers 1, 2, 3 can never run dry when each has a slot for every sender (divisor 1) -- and a policy that climbs
-// towards the rate limit on every link (what PPO learns on generous links) does need most of that.  An MI355X has 288 GB: the
-// pools get what a third of the memory that is free right now pays for, the largest tier halved first (round 3 sized them
-// for U(-1, 1) policies -- divisors 2, 8, 32, measured need ~25 %, ~2 %, ~0.02 % of the senders -- and a saturating policy
-// ended a training run with PCC_FLAG_POOL_EXHAUSTED); those divisors are the floor.  pcc_set_ring_pools overrides.
-int ensure_pools(pcc_sim_t *sim) {
-    if (!sim->pools_pending) return PCC_OK;
-    Dev &d = sim->d;
-    unsigned div[kMaxTiers] = {1, 1, 1, 1};
-    const unsigned floor_div[kMaxTiers] = {1, 2, 8, 32};
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) free_b = 0;
-    const double budget = 0.33 * (double)free_b;
-    const double senders = (double)d.n * d.ns;
-    auto tier_bytes = [&](int c) { return senders / div[c] * 3.0 * (double)((size_t)d.cap0 << (2 * c)) * sizeof(double2); };
-    for (;;) {
-        double total = 0.0;
-        int big = -1;
-        for (int c = 1; c < d.n_tiers; c++) {
-            total += tier_bytes(c);
-            if (div[c] < floor_div[c] && (big < 0 || tier_bytes(c) > tier_bytes(big))) big = c;
-        }
-        if (total <= budget || big < 0) break;
-        div[big] *= 2;
-    }
-    return alloc_pools(sim, div);
-}
-}  // namespace
 
 int pcc_set_ring_pools(pcc_sim_t *sim, uint32_t div1, uint32_t div2, uint32_t div3) {
     if (!sim) return fail(PCC_EINVAL, "sim is NULL");
@@ -921,16 +952,7 @@ int pcc_set_ring_pools(pcc_sim_t *sim, uint32_t div1, uint32_t div2, uint32_t di
     const unsigned div[kMaxTiers] = {1, div1, div2, div3};
     for (int c = 1; c < kMaxTiers; c++)
         if (div[c] < 1) return fail(PCC_EINVAL, "pool divisors must be >= 1 (1 = a slot for every sender)");
-    DeviceGuard guard(sim->device);
-    if (hipDeviceSynchronize() != hipSuccess) return fail(PCC_EHIP, "hipDeviceSynchronize failed");
-    Dev &d = sim->d;
-    { const int rc = alloc_pools(sim, div); if (rc != PCC_OK) return rc; }
-    launch_forget_ring_slots(d, nullptr);
-    if (hipDeviceSynchronize() != hipSuccess) return fail(PCC_EHIP, "forget_ring_slots_kernel failed");
-    sim->ever_reset = false;  // whatever was in flight lived in the old pools: a reset must follow
-    sim->restarts_pending = false;
-    sim->read_buf = -1;
-    return PCC_OK;
+    return rebuild_pools(sim, sim->d.parts, div);   // (whatever was in flight lived in the old pools)
 }
 
 // The event-loop build (event_engine) runs the interval when packets can overtake each other (latency noise) and when
@@ -966,8 +988,7 @@ int update_engine(pcc_sim_t *sim) {
         sim->d.noise_cap = sim->ring_capacity;
     }
     sim->d.engine = engine;
-    sim->ever_reset = false;  // in-flight accounting differs / lives in another structure: a reset must follow
-    sim->read_buf = -1;
+    need_full_reset(sim);  // in-flight accounting differs / lives in another structure
     return PCC_OK;
 }
 
@@ -1066,16 +1087,17 @@ void queue_refill(pcc_sim_t *sim, hipStream_t st) {
     const uint32_t seq = sim->step_seq - 1u, row = seq & 3u;
     if (hipEventRecord(sim->ev_ret, st) != hipSuccess) return;
     (void)hipStreamWaitEvent(sim->aux_restart, sim->ev_ret, 0);
-    const unsigned grid = (unsigned)(sim->cu_count < (d.n + 3) / 4 ? sim->cu_count : (d.n + 3) / 4);
-    launch_refill(d, grid, sim->aux_restart, row, seq);
+    launch_refill(d, few_envs_grid(sim), sim->aux_restart, row, seq);
     (void)hipMemsetAsync(d.refill_count + row * kCntStride, 0, sizeof(uint32_t), sim->aux_restart);
     (void)hipEventRecord(sim->ev_refill[row], sim->aux_restart);
     sim->refill_recorded[row] = true;
 }
 
-// host bookkeeping after the MI of a step: episode boundary, auto-reset (ns:444, the gym wrapper's reset)
-int after_mi(pcc_sim_t *sim, float *obs_out, int auto_reset, hipStream_t st) {
+// After the launches of a step (restart: its restart_mode): the shadows' refill, then the host's bookkeeping -- episode
+// boundary, auto-reset (ns:444, the gym wrapper's reset)
+int after_mi(pcc_sim_t *sim, int restart, float *obs_out, int auto_reset, hipStream_t st) {
     const Dev &d = sim->d;
+    if (restart & 2) queue_refill(sim, st);
     sim->host_steps++;
     if (auto_reset) {
         // when every env is in lockstep the host knows which step finishes the episode and
@@ -1088,6 +1110,73 @@ int after_mi(pcc_sim_t *sim, float *obs_out, int auto_reset, hipStream_t st) {
         }
     } else if (sim->lockstep && sim->host_steps >= d.max_steps) {
         sim->lockstep = false;  // caller resets on its own schedule from here on
+    }
+    return PCC_OK;
+}
+
+// Whether after_mi will enqueue reset launches after the coming step (they rewrite observation rows after its retire launch): at
+// the episode boundary of a batch in lockstep, or out of lockstep when finished envs are not restarted inside the step.
+bool reset_follows(const pcc_sim_t *sim, int auto_reset) {
+    if (!auto_reset) return false;
+    const bool may_be_done = !sim->lockstep || sim->host_steps + 1u >= sim->d.max_steps;
+    return may_be_done && !restarts_in_step(sim, auto_reset);
+}
+
+// `seg` steps of a small batch in ONE launch (step_small_kernel: both halves, the loop over the steps inside, a workgroup per
+// 64 envs); step k reads its actions act_stride bytes behind step k - 1's -- or takes them from the policy in the loop (pol)
+int launch_small(pcc_sim_t *sim, const void *actions, int actions_f64, const StepOut &out, int seg, int64_t act_stride,
+                 const PolicyArgs *pol, hipStream_t st) {
+    next_step_seq(sim, st);
+    launch_step_small(sim->d, sim->d.rng_mode == PCC_RNG_TRACE, st, actions, actions_f64, out.obs, out.reward, out.done, out.steps, seg,
+                      act_stride, pol);
+    return check_hip(hipGetLastError(), "step kernel launch");
+}
+
+// ONE step, what pcc_step is after its argument checks.  pol: the policy in the epilogue of the retire launch (pcc_rollout;
+// only for a batch with work lists, and never as the one-launch step: launch_mi)
+int step_once(pcc_sim_t *sim, const void *actions, int actions_f64, const StepOut &out, int auto_reset, hipStream_t st,
+              const PolicyArgs *pol = nullptr) {
+    int rc, restart = 0;
+    if (!uses_lists(sim) && !sim->d.engine) {
+        rc = launch_small(sim, actions, actions_f64, out, 1, 0, nullptr, st);
+    } else {
+        next_step_seq(sim, st);
+        restart = restart_mode(sim, auto_reset);
+        rc = launch_mi(sim, 0, 0, 0, 0, restart, actions, actions_f64, out, st, pol);
+    }
+    return rc != PCC_OK ? rc : after_mi(sim, restart, out.obs, auto_reset, st);
+}
+
+// A call of several steps that stops at step t says how far the batch got (its clocks have advanced that many steps)
+int stopped(int rc, const char *call, int t, int n_steps) {
+    char why[400];
+    snprintf(why, sizeof why, "%s", g_err);
+    return fail(rc, "%s stopped after %d of %d steps: %s", call, t, n_steps, why);
+}
+
+// Whether n_steps steps can run as segments (walk_segments): a small batch whose episode boundaries the host knows, or that is
+// never reset here
+bool steps_in_segments(const pcc_sim_t *sim, int auto_reset) {
+    return !uses_lists(sim) && !sim->d.engine && (sim->lockstep || !auto_reset);
+}
+
+// ... and those steps: the steps up to the next episode boundary are ONE launch -- launch(t, seg) enqueues steps t .. t + seg - 1
+// with outputs from row t of `out` -- and the boundary's reset rewrites the observation row of the segment's last step.
+int walk_segments(pcc_sim_t *sim, const char *call, int n_steps, const StepOut &out, int auto_reset, hipStream_t st,
+                  const std::function<int(int, int)> &launch) {
+    const Dev &d = sim->d;
+    for (int t = 0, seg; t < n_steps; t += seg) {
+        seg = n_steps - t;
+        if (sim->lockstep && auto_reset) {
+            const int left = (int)d.max_steps - (int)sim->host_steps;
+            if (seg > (left > 1 ? left : 1)) seg = left > 1 ? left : 1;
+        }
+        int rc = launch(t, seg);
+        if (rc == PCC_OK) {
+            sim->host_steps += (uint32_t)(seg - 1);
+            rc = after_mi(sim, 0, row_of(d, out, t + seg - 1).obs, auto_reset, st);
+        }
+        if (rc != PCC_OK) return stopped(rc, call, t, n_steps);
     }
     return PCC_OK;
 }
@@ -1112,11 +1201,10 @@ int pcc_step_retire(pcc_sim_t *sim, float *obs_out, float *reward_out, uint8_t *
     DeviceGuard guard(sim->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int restart = restart_mode(sim, auto_reset);
-    const int rc = launch_retire_half(sim, 0, 0, 0, 0, restart, obs_out, reward_out, done_out, steps_out, st);
+    const int rc = launch_retire_half(sim, 0, 0, 0, 0, restart, StepOut{obs_out, reward_out, done_out, steps_out}, st);
     if (rc != PCC_OK) return rc;
-    if (restart & 2) queue_refill(sim, st);
     sim->send_pending = false;
-    return after_mi(sim, obs_out, auto_reset, st);
+    return after_mi(sim, restart, obs_out, auto_reset, st);
 }
 
 int pcc_step(pcc_sim_t *sim, const void *actions, int actions_f64, float *obs_out, float *reward_out,
@@ -1125,21 +1213,7 @@ int pcc_step(pcc_sim_t *sim, const void *actions, int actions_f64, float *obs_ou
     if (!sim->ever_reset) return fail(PCC_ESTATE, "pcc_step before pcc_reset (the reference raises TypeError: run_dur is None)");
     if (sim->send_pending) return fail(PCC_ESTATE, "pcc_step between pcc_step_send and pcc_step_retire");
     DeviceGuard guard(sim->device);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    next_step_seq(sim, st);
-    const Dev &d = sim->d;
-    if (d.n < (int64_t)sim->list_min_envs && !d.engine) {
-        // a small batch: both halves in one launch (step_small_kernel)
-        launch_step_small(d, d.rng_mode == PCC_RNG_TRACE, st, actions, actions_f64, obs_out, reward_out, done_out, steps_out, 1, 0);
-        const int rc0 = check_hip(hipGetLastError(), "step kernel launch");
-        if (rc0 != PCC_OK) return rc0;
-        return after_mi(sim, obs_out, auto_reset, st);
-    }
-    const int restart = restart_mode(sim, auto_reset);
-    const int rc = launch_mi(sim, 0, 0, 0, 0, restart, actions, actions_f64, obs_out, reward_out, done_out, steps_out, st);
-    if (rc != PCC_OK) return rc;
-    if (restart & 2) queue_refill(sim, st);
-    return after_mi(sim, obs_out, auto_reset, st);
+    return step_once(sim, actions, actions_f64, StepOut{obs_out, reward_out, done_out, steps_out}, auto_reset, static_cast<hipStream_t>(stream));
 }
 
 int pcc_step_many(pcc_sim_t *sim, const void *actions, int actions_f64, int n_steps, float *obs_out, float *reward_out,
@@ -1148,60 +1222,22 @@ int pcc_step_many(pcc_sim_t *sim, const void *actions, int actions_f64, int n_st
     // (what pcc_step would refuse is refused before the first step: after that only a failing launch can stop the loop)
     if (!sim->ever_reset) return fail(PCC_ESTATE, "pcc_step_many before pcc_reset (the reference raises TypeError: run_dur is None)");
     if (sim->send_pending) return fail(PCC_ESTATE, "pcc_step_many between pcc_step_send and pcc_step_retire");
+    DeviceGuard guard(sim->device);
     const Dev &d = sim->d;
-    const size_t row = (size_t)d.n * d.ns;
-    const size_t act_row = row * (d.use_cwnd ? 2u : 1u) * (actions_f64 ? sizeof(double) : sizeof(float));
+    const size_t act_row = (size_t)d.n * d.ns * (d.use_cwnd ? 2u : 1u) * (actions_f64 ? sizeof(double) : sizeof(float));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    auto obs_at = [&](int t) { return obs_out ? obs_out + (size_t)t * row * d.HF : nullptr; };
-    int t = 0;
-    if (d.n < (int64_t)sim->list_min_envs && !d.engine && (sim->lockstep || !auto_reset)) {
-        // a small batch whose episode boundaries the host knows (or that is never reset here): the steps up to the next
-        // boundary are ONE launch -- the loop over them runs inside step_small_kernel, a workgroup per 64 envs
-        DeviceGuard guard(sim->device);
-        while (t < n_steps) {
-            int seg = n_steps - t;
-            if (sim->lockstep && auto_reset) {
-                const int left = (int)d.max_steps - (int)sim->host_steps;
-                if (seg > (left > 1 ? left : 1)) seg = left > 1 ? left : 1;
-            }
-            next_step_seq(sim, st);
-            launch_step_small(d, d.rng_mode == PCC_RNG_TRACE, st, static_cast<const char *>(actions) + (size_t)t * act_row, actions_f64,
-                              obs_at(t), reward_out ? reward_out + (size_t)t * row : nullptr, done_out ? done_out + (size_t)t * d.n : nullptr,
-                              steps_out ? steps_out + (size_t)t * row * PCC_STEP_COLS : nullptr, seg, (int64_t)act_row);
-            int rc = check_hip(hipGetLastError(), "step kernel launch");
-            sim->host_steps += (uint32_t)(seg - 1);
-            if (rc == PCC_OK) rc = after_mi(sim, obs_at(t + seg - 1), auto_reset, st);  // (the boundary's reset writes that step's observation row)
-            if (rc != PCC_OK) {
-                char why[400];
-                snprintf(why, sizeof why, "%s", g_err);
-                return fail(rc, "pcc_step_many stopped after %d of %d steps: %s", t, n_steps, why);
-            }
-            t += seg;
-        }
-        return PCC_OK;
-    }
-    for (; t < n_steps; t++) {
-        const int rc = pcc_step(sim, static_cast<const char *>(actions) + (size_t)t * act_row, actions_f64, obs_at(t),
-                                reward_out ? reward_out + (size_t)t * row : nullptr, done_out ? done_out + (size_t)t * d.n : nullptr,
-                                steps_out ? steps_out + (size_t)t * row * PCC_STEP_COLS : nullptr, auto_reset, stream);
-        if (rc != PCC_OK) {  // a launch failed: say how far the batch got (its clocks have advanced that many steps)
-            char why[400];
-            snprintf(why, sizeof why, "%s", g_err);
-            return fail(rc, "pcc_step_many stopped after %d of %d steps: %s", t, n_steps, why);
-        }
+    const StepOut out{obs_out, reward_out, done_out, steps_out};   // step t writes row t of each: so does the reset that follows it
+    auto act_at = [&](int t) { return static_cast<const char *>(actions) + (size_t)t * act_row; };
+    if (steps_in_segments(sim, auto_reset))
+        return walk_segments(sim, "pcc_step_many", n_steps, out, auto_reset, st, [&](int t, int seg) {
+            return launch_small(sim, act_at(t), actions_f64, row_of(d, out, t), seg, (int64_t)act_row, nullptr, st);
+        });
+    for (int t = 0; t < n_steps; t++) {
+        const int rc = step_once(sim, act_at(t), actions_f64, row_of(d, out, t), auto_reset, st);
+        if (rc != PCC_OK) return stopped(rc, "pcc_step_many", t, n_steps);
     }
     return PCC_OK;
 }
-
-namespace {
-// Whether after_mi will enqueue reset launches after the coming step (they rewrite observation rows after its retire launch): at
-// the episode boundary of a batch in lockstep, or out of lockstep when finished envs are not restarted inside the step.
-bool reset_follows(const pcc_sim_t *sim, int auto_reset) {
-    if (!auto_reset) return false;
-    const bool may_be_done = !sim->lockstep || sim->host_steps + 1u >= sim->d.max_steps;
-    return may_be_done && !restarts_in_step(sim, auto_reset);
-}
-}  // namespace
 
 int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps, const float *noise, float *obs_io, float *act_out,
                 float *logp_out, float *value_out, float *reward_out, uint8_t *done_out, double *steps_out, int auto_reset,
@@ -1230,24 +1266,18 @@ int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps
     }
     const int act_rows = act_out ? 0 : 2;
     auto act_at = [&](int t) { return act + (size_t)(act_rows ? t % act_rows : t) * row; };
-    auto obs_at = [&](int t) { return obs_io + (size_t)t * row * D; };
-    auto rew_at = [&](int t) { return reward_out ? reward_out + (size_t)t * row : nullptr; };
-    auto done_at = [&](int t) { return done_out ? done_out + (size_t)t * d.n : nullptr; };
-    auto steps_at = [&](int t) { return steps_out ? steps_out + (size_t)t * row * PCC_STEP_COLS : nullptr; };
+    // Step t reads observation row t of obs_io and writes row t + 1: the outputs' first rows are obs_io's row 1 and row 0 of the
+    // others.  (So the reset behind step t rewrites obs_io's row t + 1, where pcc_step_many's rewrites row t of its obs_out.)
+    const StepOut out{obs_io + row * D, reward_out, done_out, steps_out};
     // the policy on observation row t, as one stand-alone launch (pcc_policy_act)
     auto policy = [&](int t) -> int {
-        const int rc = pcc_policy_act(obs_at(t), (int64_t)row, D, params, h1, h2, noise ? noise + (size_t)t * row : nullptr, nullptr,
+        const int rc = pcc_policy_act(obs_io + (size_t)t * row * D, (int64_t)row, D, params, h1, h2, noise ? noise + (size_t)t * row : nullptr, nullptr,
                                       act_at(t), logp_out ? logp_out + (size_t)t * row : nullptr,
                                       value_out ? value_out + (size_t)t * row : nullptr, stream);
         if (rc == -2) return fail(PCC_EINVAL, "pcc_policy_act has no kernel for observation length %d with hidden sizes (%d, %d)", D, h1, h2);
         if (rc == -1) return fail(PCC_EINVAL, "pcc_policy_act refuses hidden sizes (%d, %d) at observation length %d", h1, h2, D);
         if (rc != 0) return fail(PCC_EHIP, "policy kernel launch: %s", hipGetErrorString(hipGetLastError()));
         return PCC_OK;
-    };
-    auto stopped = [&](int rc, int t) -> int {
-        char why[400];
-        snprintf(why, sizeof why, "%s", g_err);
-        return fail(rc, "pcc_rollout stopped after %d of %d steps: %s", t, n_steps, why);
     };
     // The policy inside the env's launches: the reference's --arch 32,16 (at an observation length the stand-alone FIXED kernel has
     // an instantiation for: the epilogue gives its bits; other hidden sizes of pcc_policy_act's domain run launch by launch), one sender, the send + retire launches (no event loop, no one-launch step)
@@ -1260,61 +1290,27 @@ int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps
     const bool fixed_net = h1 == kPolH1 && h2 == kPolH2 && fixed_len;
     const bool in_step = fixed_net && d.ns == 1 && !d.engine;
     PolicyArgs pa{params, PolicyLayout(D, kPolH1, kPolH2).n_params(), D, act_rows, 0, noise, act, logp_out, value_out};
-    if (in_step && d.n >= (int64_t)sim->list_min_envs && !sim->fused && sim->rollout_epilogue) {
-        // Epilogue path (PCC_TUNE_ROLLOUT_EPILOGUE; off by default: measured slower than the launches it replaces):
-        // the retire launch of step t computes the action of step t + 1 -- unless reset launches follow the step (they rewrite
-        // observation rows after it): then a stand-alone policy launch behind them.  Step 0 has one too; the last step of the
-        // call runs plain.
-        bool need = true;
-        for (int t = 0; t < n_steps; t++) {
-            int rc = need ? policy(t) : PCC_OK;
-            const bool epi = t + 1 < n_steps && !reset_follows(sim, auto_reset);
-            if (rc == PCC_OK) {
-                next_step_seq(sim, st);
-                const int restart = restart_mode(sim, auto_reset);
-                rc = launch_send(sim, 0, 0, 0, act_at(t), 0, st);
-                pa.t0 = t;
-                if (rc == PCC_OK)
-                    rc = launch_retire_half(sim, 0, 0, 0, 0, restart, obs_at(t + 1), rew_at(t), done_at(t), steps_at(t), st,
-                                            epi ? &pa : nullptr);
-                if (rc == PCC_OK && (restart & 2)) queue_refill(sim, st);
-                if (rc == PCC_OK) rc = after_mi(sim, obs_at(t + 1), auto_reset, st);
-            }
-            if (rc != PCC_OK) return stopped(rc, t);
-            need = !epi;
-        }
-        return PCC_OK;
-    }
-    if (in_step && d.n < (int64_t)sim->list_min_envs && (sim->lockstep || !auto_reset)) {
+    if (in_step && steps_in_segments(sim, auto_reset))
         // Small-batch loop path: the steps up to the next episode boundary are ONE launch of step_small_policy_kernel (as in
         // pcc_step_many), the policy in its loop; the first action of every segment from a stand-alone policy launch
-        int t = 0;
-        while (t < n_steps) {
-            int seg = n_steps - t;
-            if (sim->lockstep && auto_reset) {
-                const int left = (int)d.max_steps - (int)sim->host_steps;
-                if (seg > (left > 1 ? left : 1)) seg = left > 1 ? left : 1;
-            }
-            int rc = policy(t);
-            if (rc == PCC_OK) {
-                next_step_seq(sim, st);
-                pa.t0 = t;
-                launch_step_small(d, d.rng_mode == PCC_RNG_TRACE, st, nullptr, 0, obs_at(t + 1), rew_at(t), done_at(t), steps_at(t), seg, 0,
-                                  &pa);
-                rc = check_hip(hipGetLastError(), "step kernel launch");
-                sim->host_steps += (uint32_t)(seg - 1);
-                if (rc == PCC_OK) rc = after_mi(sim, obs_at(t + seg), auto_reset, st);
-            }
-            if (rc != PCC_OK) return stopped(rc, t);
-            t += seg;
-        }
-        return PCC_OK;
-    }
-    // Launch by launch: the contract's loop as it reads
+        return walk_segments(sim, "pcc_rollout", n_steps, out, auto_reset, st, [&](int t, int seg) {
+            const int rc = policy(t);
+            pa.t0 = t;
+            return rc != PCC_OK ? rc : launch_small(sim, nullptr, 0, row_of(d, out, t), seg, 0, &pa, st);
+        });
+    // Epilogue path (PCC_TUNE_ROLLOUT_EPILOGUE; off by default: measured slower than the launches it replaces):
+    // the retire launch of step t computes the action of step t + 1 -- unless reset launches follow the step (they rewrite
+    // observation rows after it): then a stand-alone policy launch behind them.  Step 0 has one too; the last step of the
+    // call runs plain.  Every other configuration: launch by launch, the contract's loop as it reads.
+    const bool epilogue = in_step && uses_lists(sim) && !sim->fused && sim->rollout_epilogue;
+    bool need = true;
     for (int t = 0; t < n_steps; t++) {
-        int rc = policy(t);
-        if (rc == PCC_OK) rc = pcc_step(sim, act_at(t), 0, obs_at(t + 1), rew_at(t), done_at(t), steps_at(t), auto_reset, stream);
-        if (rc != PCC_OK) return stopped(rc, t);
+        int rc = need ? policy(t) : PCC_OK;
+        const bool epi = epilogue && t + 1 < n_steps && !reset_follows(sim, auto_reset);
+        pa.t0 = t;
+        if (rc == PCC_OK) rc = step_once(sim, act_at(t), 0, row_of(d, out, t), auto_reset, st, epi ? &pa : nullptr);
+        if (rc != PCC_OK) return stopped(rc, "pcc_rollout", t, n_steps);
+        need = !epi;
     }
     return PCC_OK;
 }

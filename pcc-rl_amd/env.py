@@ -98,14 +98,8 @@ class BatchedNetworkEnv(object):
             # library sizes the pools from the free device memory (a slot for every sender where a third of it pays for that,
             # never less than divisors 2, 8, 32): a policy that saturates every link cannot run them dry
             check(L.pcc_set_ring_pools(self._h, *[int(v) for v in ring_pools]))
-        if self.DEFAULT_LIST_MIN_ENVS is not None:
-            check(L.pcc_set_tuning(self._h, 12, float(self.DEFAULT_LIST_MIN_ENVS)))
-        if self.DEFAULT_FUSED is not None:
-            check(L.pcc_set_tuning(self._h, 26, float(self.DEFAULT_FUSED)))
-        if self.DEFAULT_FUSED_ACQUIRE is not None:
-            check(L.pcc_set_tuning(self._h, 27, float(self.DEFAULT_FUSED_ACQUIRE)))
-        if self.DEFAULT_NOISE_SORTED is not None:
-            check(L.pcc_set_tuning(self._h, 33, float(self.DEFAULT_NOISE_SORTED)))
+        self.set_tuning(list_min_envs=self.DEFAULT_LIST_MIN_ENVS, fused=self.DEFAULT_FUSED, fused_acquire=self.DEFAULT_FUSED_ACQUIRE,
+                        noise_sorted=self.DEFAULT_NOISE_SORTED)
         check(L.pcc_set_delta_scale(self._h, float(DELTA_SCALE if delta_scale is None else delta_scale)))
         check(L.pcc_set_max_steps(self._h, self.max_steps))
         # the reference's dormant USE_CWND engine option (ns:54): window-limited sending, actions
@@ -190,22 +184,16 @@ class BatchedNetworkEnv(object):
         check(self._L.pcc_set_rng(self._h, native.PCC_RNG_TRACE, _ptr(t), t.shape[1]))
         self._trace = t
 
-    def set_tuning(self, round_packets=None, takeover_lanes=None, send_envs_per_wave=None, heavy_predict=None,
-                   send_waves=None, team_predict=None, heavy_item_packets=None, retire_wide_predict=None, list_min_envs=None,
-                   retire_sorted=None, light_snake=None, wave_oldest_first=None, prio_level=None, prio_light_items=None,
-                   prio_wave_items=None, prio_team=None, retire_grid_frac=None, restart_fork=None, parts=None, light_half_predict=None,
-                   fused=None, fused_acquire=None, fused_light_wgs=None, fused_max_naps=None, fused_partial_naps=None, fused_debug=None, fused_light_front=None,
-                   noise_sorted=None, light_wgs=None, light_front=None):
-        """Performance knobs (results do not depend on them); see pcc_set_tuning in include/pcc_sim.h.  `parts` (the
-        partitioning of the batch) must be followed by reset()."""
-        for key, value in ((2, round_packets), (3, takeover_lanes), (4, send_envs_per_wave), (5, heavy_predict),
-                           (8, send_waves), (9, team_predict), (10, heavy_item_packets), (11, retire_wide_predict), (12, list_min_envs),
-                           (13, retire_sorted), (14, light_snake), (15, wave_oldest_first), (16, prio_level), (17, prio_light_items),
-                           (18, prio_wave_items), (19, prio_team), (22, retire_grid_frac), (23, restart_fork), (24, parts), (25, light_half_predict),
-                           (26, fused), (27, fused_acquire), (28, fused_light_wgs), (29, fused_max_naps), (30, fused_partial_naps), (31, fused_debug), (32, fused_light_front),
-                           (33, noise_sorted), (34, light_wgs), (35, light_front)):
-            if value is not None:
-                check(self._L.pcc_set_tuning(self._h, key, float(value)))
+    def set_tuning(self, **knobs):
+        """Performance knobs (results do not depend on them): the names of native.TUNE, see pcc_set_tuning in include/pcc_sim.h;
+        None leaves a knob alone.  They are set in the order of their keys.  `parts` (the partitioning of the batch) must be
+        followed by reset()."""
+        unknown = sorted(set(knobs) - set(native.TUNE))
+        if unknown:
+            raise TypeError("set_tuning() got an unexpected keyword argument %r" % unknown[0])
+        for name, key in native.TUNE.items():
+            if knobs.get(name) is not None:
+                check(self._L.pcc_set_tuning(self._h, key, float(knobs[name])))
 
     def seed(self, seed=None):
         if seed is not None:
@@ -233,22 +221,37 @@ class BatchedNetworkEnv(object):
             self._t = 0
         return self._out(self._obs)
 
-    def _actions(self, actions):
+    def _actions(self, actions, steps=False):
+        """The actions as the library reads them -- float32 or float64, contiguous, on the env's device, [n_envs, width] or with
+        `steps` [T, n_envs * width] -- and the library's actions_f64 flag."""
         a = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions), device=self.device)
         if a.device != self.device:
             a = a.to(self.device)
         if a.dtype not in (torch.float32, torch.float64):
             a = a.to(torch.float32)
         width = self.n_senders * self.action_dim
-        if a.numel() != self.n_envs * width:
+        if steps:
+            T = int(a.shape[0])
+            if T < 1 or a.numel() != T * self.n_envs * width:
+                raise ValueError("actions has %d elements, expected T * n_envs * %d" % (a.numel(), width))
+            a = a.reshape(T, self.n_envs * width)
+        elif a.numel() != self.n_envs * width:
             raise ValueError("actions has %d elements, expected n_envs * %d = %d"
                              % (a.numel(), width, self.n_envs * width))
-        return a.reshape(self.n_envs, width).contiguous()
+        else:
+            a = a.reshape(self.n_envs, width)
+        return a.contiguous(), 1 if a.dtype == torch.float64 else 0
+
+    def _check_out(self, what, t, numel, dtypes=(torch.float32,)):
+        """An output tensor of `what` (None = not wanted): numel elements (None = any) of one of dtypes, contiguous, on the env's device."""
+        if t is not None and ((numel is not None and t.numel() != numel) or t.dtype not in dtypes or not t.is_contiguous()
+                              or t.device != self.device):
+            raise ValueError("%s tensor has the wrong size, dtype, layout or device" % what)
 
     def step_send(self, actions):
         """First half of step(): apply the actions and transmit the coming monitor interval's packets."""
-        a = self._actions(actions)
-        check(self._L.pcc_step_send(self._h, _ptr(a), 1 if a.dtype == torch.float64 else 0, self._stream()))
+        a, f64 = self._actions(actions)
+        check(self._L.pcc_step_send(self._h, _ptr(a), f64, self._stream()))
 
     def step_retire(self):
         """Second half of step(): acknowledgements, losses, metrics; returns what step() returns."""
@@ -267,8 +270,8 @@ class BatchedNetworkEnv(object):
     def step(self, actions):
         """One monitor interval for every env (ns:407-446 batched): obs, reward, done, info.  One
         library call (pcc_step: two launches, the send half and the retire half)."""
-        a = self._actions(actions)
-        check(self._L.pcc_step(self._h, _ptr(a), 1 if a.dtype == torch.float64 else 0, _ptr(self._obs),
+        a, f64 = self._actions(actions)
+        check(self._L.pcc_step(self._h, _ptr(a), f64, _ptr(self._obs),
                                _ptr(self._reward), _ptr(self._done), _ptr(self._steps),
                                1 if self.auto_reset else 0, self._stream()))
         return self._step_result()
@@ -277,13 +280,12 @@ class BatchedNetworkEnv(object):
         """step() that writes straight into the caller's tensors -- e.g. rows of a rollout buffer -- instead of the
         env's own output buffers: obs_out float32 [N, S, H*F] (or [N, H*F] with one sender), reward_out float32 [N, S]
         ([N]), done_out uint8/bool [N], all contiguous on the env's device.  Returns nothing; no copy is made."""
-        a = self._actions(actions)
-        N, S, D = self.n_envs, self.n_senders, self.obs_dim
-        for t, n, dt in ((obs_out, N * S * D, (torch.float32,)), (reward_out, N * S, (torch.float32,)),
-                         (done_out, N, (torch.uint8, torch.bool))):
-            if t.numel() != n or t.dtype not in dt or not t.is_contiguous() or t.device != self.device:
-                raise ValueError("step_into: an output tensor has the wrong size, dtype, layout or device")
-        check(self._L.pcc_step(self._h, _ptr(a), 1 if a.dtype == torch.float64 else 0, _ptr(obs_out), _ptr(reward_out),
+        a, f64 = self._actions(actions)
+        N, S = self.n_envs, self.n_senders
+        self._check_out("step_into: an output", obs_out, N * S * self.obs_dim)
+        self._check_out("step_into: an output", reward_out, N * S)
+        self._check_out("step_into: an output", done_out, N, (torch.uint8, torch.bool))
+        check(self._L.pcc_step(self._h, _ptr(a), f64, _ptr(obs_out), _ptr(reward_out),
                                _ptr(done_out), _ptr(self._steps), 1 if self.auto_reset else 0, self._stream()))
         self._t += 1
 
@@ -294,22 +296,13 @@ class BatchedNetworkEnv(object):
         For open-loop drivers of small batches: below ``list_min_envs`` envs, in lockstep, the steps up to the next episode
         boundary run inside one launch.  If the call fails part-way the error says after how many steps; the env's step
         counter is not advanced then (reset before going on)."""
-        a = actions if torch.is_tensor(actions) else torch.as_tensor(np.asarray(actions), device=self.device)
-        if a.device != self.device:
-            a = a.to(self.device)
-        if a.dtype not in (torch.float32, torch.float64):
-            a = a.to(torch.float32)
-        T = int(a.shape[0])
-        width = self.n_senders * self.action_dim
-        if T < 1 or a.numel() != T * self.n_envs * width:
-            raise ValueError("actions has %d elements, expected T * n_envs * %d" % (a.numel(), width))
-        a = a.reshape(T, self.n_envs * width).contiguous()
-        N, S, D = self.n_envs, self.n_senders, self.obs_dim
-        for t, n, dt in ((obs_out, T * N * S * D, (torch.float32,)), (reward_out, T * N * S, (torch.float32,)),
-                         (done_out, T * N, (torch.uint8, torch.bool)), (steps_out, T * N * S * native.PCC_STEP_COLS, (torch.float64,))):
-            if t is not None and (t.numel() != n or t.dtype not in dt or not t.is_contiguous() or t.device != self.device):
-                raise ValueError("step_many: an output tensor has the wrong size, dtype, layout or device")
-        check(self._L.pcc_step_many(self._h, _ptr(a), 1 if a.dtype == torch.float64 else 0, T, _ptr(obs_out), _ptr(reward_out),
+        a, f64 = self._actions(actions, steps=True)
+        T, N, S = int(a.shape[0]), self.n_envs, self.n_senders
+        self._check_out("step_many: an output", obs_out, T * N * S * self.obs_dim)
+        self._check_out("step_many: an output", reward_out, T * N * S)
+        self._check_out("step_many: an output", done_out, T * N, (torch.uint8, torch.bool))
+        self._check_out("step_many: an output", steps_out, T * N * S * native.PCC_STEP_COLS, (torch.float64,))
+        check(self._L.pcc_step_many(self._h, _ptr(a), f64, T, _ptr(obs_out), _ptr(reward_out),
                                     _ptr(done_out), _ptr(steps_out), 1 if self.auto_reset else 0, self._stream()))
         self._t += T
 
@@ -328,15 +321,13 @@ class BatchedNetworkEnv(object):
             raise ValueError("rollout: obs_b needs T + 1 >= 2 rows")
         if len(arch) != 2:
             raise ValueError("rollout: arch must be two hidden sizes")
-        N, S, D = self.n_envs, self.n_senders, self.obs_dim
-        for t, n, dt in ((obs_b, (T + 1) * N * S * D, (torch.float32,)), (params, None, (torch.float32,)),
-                         (noise, T * N * S, (torch.float32,)), (act_b, T * N * S, (torch.float32,)),
-                         (logp_b, T * N * S, (torch.float32,)), (val_b, T * N * S, (torch.float32,)),
-                         (rew_b, T * N * S, (torch.float32,)), (done_b, T * N, (torch.uint8, torch.bool)),
-                         (steps_b, T * N * S * native.PCC_STEP_COLS, (torch.float64,))):
-            if t is not None and ((n is not None and t.numel() != n) or t.dtype not in dt or not t.is_contiguous()
-                                  or t.device != self.device):
-                raise ValueError("rollout: a tensor has the wrong size, dtype, layout or device")
+        N, S = self.n_envs, self.n_senders
+        self._check_out("rollout: a", obs_b, (T + 1) * N * S * self.obs_dim)
+        self._check_out("rollout: a", params, None)
+        for t in (noise, act_b, logp_b, val_b, rew_b):
+            self._check_out("rollout: a", t, T * N * S)
+        self._check_out("rollout: a", done_b, T * N, (torch.uint8, torch.bool))
+        self._check_out("rollout: a", steps_b, T * N * S * native.PCC_STEP_COLS, (torch.float64,))
         check(self._L.pcc_rollout(self._h, _ptr(params), int(arch[0]), int(arch[1]), T, _ptr(noise), _ptr(obs_b), _ptr(act_b),
                                   _ptr(logp_b), _ptr(val_b), _ptr(rew_b), _ptr(done_b), _ptr(steps_b),
                                   1 if self.auto_reset else 0, self._stream()))

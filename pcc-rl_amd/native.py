@@ -28,6 +28,17 @@ FIELDS = {
     "total_sent": (21, "int64", False), "ring_tier": (22, "uint8", True), "cwnd": (23, "int32", True),
 }
 
+# knob name -> key of pcc_set_tuning: the PCC_TUNE_* enum of include/pcc_sim.h, names lower-cased, without the retired keys
+# (20, 21, 23, 34); tests/test_abi_cpu.py holds the two against each other
+TUNE = {
+    "round_packets": 2, "takeover_lanes": 3, "send_envs_per_wave": 4, "heavy_predict": 5, "send_waves": 8, "team_predict": 9,
+    "heavy_item_packets": 10, "retire_wide_predict": 11, "list_min_envs": 12, "retire_sorted": 13, "light_snake": 14,
+    "wave_oldest_first": 15, "prio_level": 16, "prio_light_items": 17, "prio_wave_items": 18, "prio_team": 19,
+    "retire_grid_frac": 22, "parts": 24, "light_half_predict": 25, "fused": 26, "fused_acquire": 27, "fused_light_wgs": 28,
+    "fused_max_naps": 29, "fused_partial_naps": 30, "fused_debug": 31, "fused_light_front": 32, "noise_sorted": 33,
+    "light_front": 35, "rollout_epilogue": 36,
+}
+
 # every symbol include/pcc_sim.h declares
 SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params", "pcc_set_param_ranges",
            "pcc_set_rng", "pcc_set_seed", "pcc_set_tuning", "pcc_set_ring_pools", "pcc_set_cwnd_mode", "pcc_set_latency_noise", "pcc_set_delta_scale", "pcc_set_max_steps", "pcc_reset", "pcc_step", "pcc_step_many", "pcc_rollout", "pcc_step_send",

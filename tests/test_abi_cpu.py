@@ -29,8 +29,22 @@ def declared_functions():
     return sorted(names)
 
 
+def declared_tuning_keys():
+    """name -> number of the PCC_TUNE_* enum of pcc_sim.h, names lower-cased, without the retired keys (their comment says `gone`)."""
+    text = open(os.path.join(ROOT, "include", "pcc_sim.h")).read()
+    keys = {}
+    for name, number, comment in re.findall(r"PCC_TUNE_([A-Z0-9_]+)\s*=\s*(\d+)\s*(?:/\*(.*?)\*/)?", text, flags=re.S):
+        if not comment.strip().startswith("gone"):
+            keys[name.lower()] = int(number)
+    return keys
+
+
 def test_header_and_binding_agree():
     assert declared_functions() == sorted(native.SYMBOLS)
+    keys = declared_tuning_keys()
+    assert len(keys) >= 29 and keys["round_packets"] == 2 and keys["rollout_epilogue"] == 36     # (the parse found the enum)
+    assert not {"split_streams", "light_front_wgs", "restart_fork", "light_wgs"} & set(keys)
+    assert keys == native.TUNE
 
 
 def test_library_exports_every_declared_symbol(libpath):

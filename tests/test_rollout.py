@@ -63,7 +63,7 @@ def _params(D, arch=(32, 16), seed=0):
 def _make(N, seed, epilogue=True, **kw):
     env = pcc_rl_amd.BatchedNetworkEnv(N, device=DEV, seed=seed, **kw)
     # PCC_TUNE_ROLLOUT_EPILOGUE: the policy in the retire launch's epilogue at full size (off by default: measured slower)
-    native.check(env._L.pcc_set_tuning(env._h, 36, 1.0 if epilogue else 0.0))
+    native.check(env._L.pcc_set_tuning(env._h, native.TUNE["rollout_epilogue"], 1.0 if epilogue else 0.0))
     env.reset()
     return env
 
@@ -166,8 +166,8 @@ def test_rollout_epilogue_16_and_8_lane_groups(wide):
     # RETIRE_WIDE_PREDICT 0 + a grid with room: as many envs as fit retired (and given their policy) by 16 lanes; 1e9: all by 8
     def make():
         env = _make(20000, 9)
-        native.check(env._L.pcc_set_tuning(env._h, 11, wide))
-        native.check(env._L.pcc_set_tuning(env._h, 22, 1.0))
+        native.check(env._L.pcc_set_tuning(env._h, native.TUNE["retire_wide_predict"], wide))
+        native.check(env._L.pcc_set_tuning(env._h, native.TUNE["retire_grid_frac"], 1.0))
         return env
     _compare(make, 24)
 

@@ -2,7 +2,7 @@
 """A/B of run-time tuning knobs on ONE handle with the settings alternating EVERY step: every setting sees every phase of the
 episodes (tools/ab_knob.py's blocks of 25 steps line up with the episode's growth of the packet counts: its first setting
 always looks best).  Send and retire launches timed apart with HIP events; the step that runs the boundary reset is left out.
-usage: ab_step.py '[{"light_wgs": 40}, {"light_wgs": 0}]' [n_envs] [episodes] [n_senders]"""
+usage: ab_step.py '[{"send_waves": 12}, {"send_waves": 13}]' [n_envs] [episodes] [n_senders]"""
 import json, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

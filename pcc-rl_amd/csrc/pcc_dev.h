@@ -690,6 +690,39 @@ __device__ __forceinline__ void fused_push(const Dev &D, const int buf, const ui
     if (lane == 0) (void)__hip_atomic_fetch_add(fq_word(D, buf, xcc, kFPushed), n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- steps that several kernels share, each in the shape that leaves every kernel's instructions as they were (tools/asm_diff.py)
+__device__ __forceinline__ double load_action(const void *actions, const int actions_f64, const int64_t k) {
+    return actions_f64 ? ((const double *)actions)[k] : (double)((const float *)actions)[k];
+}
+// apply_rate_delta + set_rate: ns:235-241, 275-281.  A NaN action counts as 0 and raises PCC_FLAG_BAD_ACTION: never silent, never in the clock
+__device__ __forceinline__ double apply_rate_delta(const Dev &D, double rate, double delta, uint32_t &flags) {
+    const double scale = D.delta_scale;
+    if (delta != delta) { delta = 0.0; flags |= PCC_FLAG_BAD_ACTION; }
+    delta *= scale;
+    rate = delta >= 0.0 ? rate * (1.0 + delta) : rate / (1.0 - delta);
+    if (rate > kMaxRate) rate = kMaxRate;
+    if (rate < kMinRate) rate = kMinRate;
+    return rate;
+}
+// apply_cwnd_delta + set_cwnd: ns:243-249, 283-289
+__device__ __forceinline__ uint32_t apply_cwnd_delta(const Dev &D, const uint32_t cw, double delta, uint32_t &flags) {
+    const double scale = D.delta_scale;
+    if (delta != delta) { delta = 0.0; flags |= PCC_FLAG_BAD_ACTION; }
+    delta *= scale;
+    const double c = delta >= 0.0 ? (double)cw * (1.0 + delta) : (double)cw / (1.0 - delta);
+    return c >= 5000.0 ? 5000u : (c < 4.0 ? 4u : (uint32_t)c);  // int(), then [MIN_CWND, MAX_CWND] (ns:33-34)
+}
+// metric `id` of an empty monitor interval, scaled as the history holds it (so:57-62: every metric is 0 but the two ratios)
+__device__ __forceinline__ float empty_history_value(const int id) {
+    return (float)(((id == PCC_M_SEND_RATIO || id == PCC_M_LATENCY_RATIO) ? 1.0 : 0.0) / c_metric_scale[id]);
+}
+// env i's shadow (block N + i) is to be refilled: listed in this step's refill row, once, whoever else lists it in this step
+__device__ __forceinline__ void list_refill(const Dev &D, EnvBlk *shadow, const int64_t i) {
+    if (shadow_list(shadow)) {
+        const uint32_t row = D.step_seq & 3u;
+        D.refill_list[(size_t)row * (size_t)D.n + atomicAdd(&D.refill_count[row * kCntStride], 1u)] = (uint32_t)i;
+    }
+}
 // (send_kernel itself follows retire_env below: a restart item runs the env's warm-up intervals through both halves)
 
 }  // namespace

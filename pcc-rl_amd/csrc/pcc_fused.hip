@@ -327,13 +327,11 @@ int resident_blocks() {
 namespace pcc {
 
 void launch_step_fused(const Dev &d, bool trace, unsigned grid, unsigned wave_wgs, unsigned light_front, hipStream_t st, int read_buf, int fill_buf, int zero_buf,
-                       int retire_on, const void *actions, int actions_f64, float *obs_out, float *reward_out, uint8_t *done_out, double *steps_out) {
-#define PCC_F(NS_, TR_)                                                                                                              \
-    hipLaunchKernelGGL((step_fused_kernel<NS_, TR_>), dim3(grid), dim3(4 * kWave), 0, st, d, read_buf, fill_buf, zero_buf, wave_wgs, light_front, retire_on, actions, \
-                       actions_f64, obs_out, reward_out, done_out, steps_out)
-    if (d.ns == 1) { if (trace) PCC_F(1, true); else PCC_F(1, false); }
-    else { if (trace) PCC_F(2, true); else PCC_F(2, false); }
-#undef PCC_F
+                       int retire_on, const Actions &act, const StepOut &out) {
+    dispatch_ns_flag(d.ns, trace, [&](auto ns, auto tr) {
+        hipLaunchKernelGGL((step_fused_kernel<decltype(ns)::value, decltype(tr)::value>), dim3(grid), dim3(4 * kWave), 0, st, d, read_buf, fill_buf,
+                           zero_buf, wave_wgs, light_front, retire_on, act.p, act.f64, out.obs, out.reward, out.done, out.steps);
+    });
 }
 
 void launch_clear_list_buffer(const Dev &d, hipStream_t st, int buf) {
@@ -341,8 +339,9 @@ void launch_clear_list_buffer(const Dev &d, hipStream_t st, int buf) {
 }
 
 int fused_resident_blocks(int ns, bool trace) {
-    if (ns == 1) return trace ? resident_blocks<1, true>() : resident_blocks<1, false>();
-    return trace ? resident_blocks<2, true>() : resident_blocks<2, false>();
+    int nb = 0;
+    dispatch_ns_flag(ns, trace, [&](auto n, auto tr) { nb = resident_blocks<decltype(n)::value, decltype(tr)::value>(); });
+    return nb;
 }
 
 }  // namespace pcc

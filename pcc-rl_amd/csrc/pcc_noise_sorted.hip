@@ -188,8 +188,9 @@ __global__ __launch_bounds__(T) void noise_sorted_kernel(Dev D, int warm, uint32
 
     const int64_t k0s = sidx(D, 0, i);
     double rate = D.snd[k0s].rate;
-    if (!warm) {   // apply_rate_delta (ns:235-241, 275-281): as the retire launch does it for the same env (it stores the rate)
-        double delta = actions_f64 ? ((const double *)actions)[i] : (double)((const float *)actions)[i];
+    if (!warm) {
+        // (apply_rate_delta's text, pcc_dev.h, without the flag: the retire launch of the same step stores the rate and reports a NaN)
+        double delta = load_action(actions, actions_f64, i);
         if (delta != delta) delta = 0.0;
         delta *= D.delta_scale;
         rate = delta >= 0.0 ? rate * (1.0 + delta) : rate / (1.0 - delta);
@@ -604,9 +605,8 @@ __global__ __launch_bounds__(T) void noise_sorted2_kernel(Dev D, int warm, uint3
     for (int s = 0; s < 2; s++) {
         const int64_t ks = sidx(D, s, i);
         rate[s] = D.snd[ks].rate;
-        if (!warm) {   // apply_rate_delta (ns:235-241, 275-281): as the retire launch does it for the same env (it stores the rate)
-            const int64_t a = i * 2 + s;
-            double delta = actions_f64 ? ((const double *)actions)[a] : (double)((const float *)actions)[a];
+        if (!warm) {   // (as in noise_sorted_kernel: apply_rate_delta's text without the flag)
+            double delta = load_action(actions, actions_f64, i * 2 + s);
             if (delta != delta) delta = 0.0;
             delta *= D.delta_scale;
             rate[s] = delta >= 0.0 ? rate[s] * (1.0 + delta) : rate[s] / (1.0 - delta);
@@ -938,20 +938,19 @@ namespace pcc {
 // One workgroup per env, two instances: up to 256 due events per hop and 128 SENDs in one go by one wavefront for most envs (a dozen
 // workgroups per compute unit; an env that does not fit is left alone), then 1 024 / 512 with sub-intervals by four wavefronts for
 // the rest (three workgroups per compute unit; it leaves at once where the first has been).
-void launch_noise_sorted(const Dev &d, hipStream_t st, int warm, uint32_t warm_mi, int gate, const void *actions, int actions_f64,
-                         int only_small) {
+void launch_noise_sorted(const Dev &d, hipStream_t st, const Warm &warm, int gate, const Actions &act, int only_small) {
     const unsigned grid = (unsigned)d.n;
     if (d.ns == 2) {   // two senders: 256 due events per hop / 128 SENDs of both senders in one go by one wavefront, then 512 / 256 with sub-intervals by two
         // (measured at 16 384 envs x 2 senders, ms per step: this pair 11.8; 1 024 / 512 by four wavefronts as the second instance
         // 15.0 -- its 62 KB of LDS leave two workgroups per compute unit; one 256 / 128 instance with sub-intervals 15.1)
-        hipLaunchKernelGGL((noise_sorted2_kernel<256, 128, 128, false, 64>), dim3(grid), dim3(64), 0, st, d, warm, warm_mi, gate, actions, actions_f64);
+        hipLaunchKernelGGL((noise_sorted2_kernel<256, 128, 128, false, 64>), dim3(grid), dim3(64), 0, st, d, warm.on, warm.mi, gate, act.p, act.f64);
         if (only_small) return;
-        hipLaunchKernelGGL((noise_sorted2_kernel<512, 256, 128, true, 128>), dim3(grid), dim3(128), 0, st, d, warm, warm_mi, gate, actions, actions_f64);
+        hipLaunchKernelGGL((noise_sorted2_kernel<512, 256, 128, true, 128>), dim3(grid), dim3(128), 0, st, d, warm.on, warm.mi, gate, act.p, act.f64);
         return;
     }
-    hipLaunchKernelGGL((noise_sorted_kernel<256, 128, 128, false, 64>), dim3(grid), dim3(64), 0, st, d, warm, warm_mi, gate, actions, actions_f64);
+    hipLaunchKernelGGL((noise_sorted_kernel<256, 128, 128, false, 64>), dim3(grid), dim3(64), 0, st, d, warm.on, warm.mi, gate, act.p, act.f64);
     if (only_small) return;
-    hipLaunchKernelGGL((noise_sorted_kernel<1024, 512, 256, true, 256>), dim3(grid), dim3(256), 0, st, d, warm, warm_mi, gate, actions, actions_f64);
+    hipLaunchKernelGGL((noise_sorted_kernel<1024, 512, 256, true, 256>), dim3(grid), dim3(256), 0, st, d, warm.on, warm.mi, gate, act.p, act.f64);
 }
 
 }  // namespace pcc

@@ -179,21 +179,18 @@ __global__ __launch_bounds__(kRetireBlock, NS == 2 ? PCC_RETIRE_OCC2 : PCC_RETIR
 
 namespace pcc {
 
-void launch_retire(const Dev &d, bool noise, unsigned grid, hipStream_t st, int read_buf, int fill_buf, int warm, uint32_t warm_mi,
-                   int last_warm, int gate, int restart, float *obs_out, float *reward_out, uint8_t *done_out, double *steps_out,
-                   const void *actions, int actions_f64, const PolicyArgs *pol) {
+void launch_retire(const Dev &d, bool noise, unsigned grid, hipStream_t st, int read_buf, int fill_buf, const Warm &warm, int gate,
+                   int restart, const StepOut &out, const Actions &act, const PolicyArgs *pol) {
     if (pol) {   // (the host only asks for it with one sender, no event loop, no warm-up interval)
         const size_t lds = (size_t)(kRetireMaxPerBlock * kPolScratch + pol->n_params) * sizeof(float);
         hipLaunchKernelGGL((retire_kernel<1, false, PolicyArgs>), dim3(grid), dim3(kRetireBlock), lds, st, d, read_buf, fill_buf, 0, 0u, 0, 0,
-                           restart, obs_out, reward_out, done_out, steps_out, nullptr, 0, *pol);
+                           restart, out.obs, out.reward, out.done, out.steps, nullptr, 0, *pol);
         return;
     }
-#define PCC_RT(NS_, NZ_)                                                                                                          \
-    hipLaunchKernelGGL((retire_kernel<NS_, NZ_>), dim3(grid), dim3(kRetireBlock), 0, st, d, read_buf, fill_buf, warm, warm_mi, last_warm, \
-                       gate, restart, obs_out, reward_out, done_out, steps_out, actions, actions_f64)
-    if (d.ns == 1) { if (noise) PCC_RT(1, true); else PCC_RT(1, false); }
-    else { if (noise) PCC_RT(2, true); else PCC_RT(2, false); }
-#undef PCC_RT
+    dispatch_ns_flag(d.ns, noise, [&](auto ns, auto nz) {
+        hipLaunchKernelGGL((retire_kernel<decltype(ns)::value, decltype(nz)::value>), dim3(grid), dim3(kRetireBlock), 0, st, d, read_buf, fill_buf,
+                           warm.on, warm.mi, warm.last, gate, restart, out.obs, out.reward, out.done, out.steps, act.p, act.f64);
+    });
 }
 
 static_assert(kRetireEnvsPerBlockNarrow == kRetireMaxPerBlock, "pcc_kernels.h tells the host how many envs a retire workgroup takes");

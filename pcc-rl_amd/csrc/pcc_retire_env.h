@@ -1020,8 +1020,7 @@ __device__ __forceinline__ void reset_env(const Dev &D, const int64_t i, float *
         for (int h = 0; i < D.n && h < D.H; h++)
             for (int f = 0; f < D.F; f++) {
                 const int id = D.fid[f];
-                const double v = (id == PCC_M_SEND_RATIO || id == PCC_M_LATENCY_RATIO) ? 1.0 : 0.0;
-                const float x = (float)(v / c_metric_scale[id]);
+                const float x = empty_history_value(id);
                 hist[h * D.F + f] = x;
                 if (obs) obs[h * D.F + f] = x;
             }
@@ -1089,18 +1088,9 @@ __device__ __forceinline__ float retire_env(const Dev &D, const int64_t i, const
             cw[s] = D.use_cwnd ? D.snd[k].cwnd : 0xFFFFFFFFu;
             if (!warm) {
                 const int64_t ar = D.use_cwnd ? 2 * (i * NS + s) : i * NS + s;  // USE_CWND: [rate action, cwnd action] per sender
-                double delta = actions_f64 ? ((const double *)actions)[ar] : (double)((const float *)actions)[ar];
-                if (delta != delta) { delta = 0.0; flags |= PCC_FLAG_BAD_ACTION; }
-                delta *= D.delta_scale;
-                rate[s] = delta >= 0.0 ? rate[s] * (1.0 + delta) : rate[s] / (1.0 - delta);
-                if (rate[s] > kMaxRate) rate[s] = kMaxRate;
-                if (rate[s] < kMinRate) rate[s] = kMinRate;
-                if (D.use_cwnd) {  // apply_cwnd_delta + set_cwnd: ns:243-249, 283-289
-                    double dc = actions_f64 ? ((const double *)actions)[ar + 1] : (double)((const float *)actions)[ar + 1];
-                    if (dc != dc) { dc = 0.0; flags |= PCC_FLAG_BAD_ACTION; }
-                    dc *= D.delta_scale;
-                    const double c = dc >= 0.0 ? (double)cw[s] * (1.0 + dc) : (double)cw[s] / (1.0 - dc);
-                    cw[s] = c >= 5000.0 ? 5000u : (c < 4.0 ? 4u : (uint32_t)c);  // int(), then [MIN_CWND, MAX_CWND] (ns:33-34)
+                rate[s] = apply_rate_delta(D, rate[s], load_action(actions, actions_f64, ar), flags);
+                if (D.use_cwnd) {
+                    cw[s] = apply_cwnd_delta(D, cw[s], load_action(actions, actions_f64, ar + 1), flags);
                     if (lead) D.snd[k].cwnd = cw[s];
                 }
             }
@@ -1396,10 +1386,8 @@ __device__ __forceinline__ float retire_env(const Dev &D, const int64_t i, const
                 float v = (x - keep) < G ? nf0 : nf1;
                 if (x < keep) v = old_row[b];
                 if (x < D.HF && !prof_skip(D, 2)) {
-                    if (restarts) {  // (the next episode's history starts empty -- whether its state is swapped in below or set up later)
-                        const int id = D.fid[x % D.F];
-                        v = (float)(((id == PCC_M_SEND_RATIO || id == PCC_M_LATENCY_RATIO) ? 1.0 : 0.0) / c_metric_scale[id]);
-                    }
+                    // (the next episode's history starts empty -- whether its state is swapped in below or set up later)
+                    if (restarts) v = empty_history_value(D.fid[x % D.F]);
                     hist[x] = v;
                     if (obs) obs[x] = v;
                 }
@@ -1410,10 +1398,7 @@ __device__ __forceinline__ float retire_env(const Dev &D, const int64_t i, const
                 float v = (x - keep) < G ? nf0 : nf1;
                 if (x < keep) v = hist[x + D.F];
                 if (x < D.HF) {
-                    if (restarts) {
-                        const int id = D.fid[x % D.F];
-                        v = (float)(((id == PCC_M_SEND_RATIO || id == PCC_M_LATENCY_RATIO) ? 1.0 : 0.0) / c_metric_scale[id]);
-                    }
+                    if (restarts) v = empty_history_value(D.fid[x % D.F]);
                     hist[x] = v;
                     if (obs) obs[x] = v;
                 }
@@ -1495,6 +1480,7 @@ __device__ __forceinline__ float retire_env(const Dev &D, const int64_t i, const
                     rates += D.snd[ks].rate;
                 }
                 filed = (float)(D.env[sh].run_dur * rates);   // (the class of the new episode's first interval)
+                // (list_refill's text, pcc_dev.h, the atomic in a statement of its own: through the helper every retire_kernel moves)
                 if (shadow_list(&D.env[sh])) {                 // consumed: the refill kernel prepares the episode after this one
                     const uint32_t row = D.step_seq & 3u;
                     const uint32_t at = atomicAdd(&D.refill_count[row * kCntStride], 1u);

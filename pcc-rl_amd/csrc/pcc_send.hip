@@ -35,7 +35,7 @@ __global__ __launch_bounds__(4 * kWave, NS == 2 ? PCC_SEND_OCC2 : PCC_SEND_OCC) 
     // auto-reset launches of a step in which no env finished have nothing to do (envs at different
     // points of their episodes: the host cannot know)
     if (gate && __hip_atomic_load(D.any_done, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != D.step_seq) return;
-    if (blockIdx.x == 0 && zero_buf >= 0) {  // the list buffer the coming retire launch files into: every partition's set
+    if (blockIdx.x == 0 && zero_buf >= 0) {  // the retire launch's list buffer (clear_list_buffer, pcc_fused.hip, as text: called, its loops are peeled, 6 000 lines move)
         for (uint32_t w = threadIdx.x; w < D.parts * (uint32_t)(kClasses + 1); w += blockDim.x)
             *cls_count_of(D, list_view(D, zero_buf, w / (uint32_t)(kClasses + 1)), w % (uint32_t)(kClasses + 1)) = 0u;
         for (uint32_t w = threadIdx.x; w < D.parts * kShards; w += blockDim.x)
@@ -69,13 +69,11 @@ __global__ __launch_bounds__(4 * kWave, NS == 2 ? PCC_SEND_OCC2 : PCC_SEND_OCC) 
 namespace pcc {
 
 void launch_send(const Dev &d, bool trace, unsigned light_wgs, unsigned wave_wgs, unsigned light_front, hipStream_t st, int read_buf,
-                 int zero_buf, int warm, uint32_t warm_mi, int gate, const void *actions, int actions_f64) {
-#define PCC_S(NS_, TR_)                                                                                                           \
-    hipLaunchKernelGGL((send_kernel<NS_, TR_>), dim3(light_wgs + wave_wgs), dim3(4 * kWave), 0, st, d, read_buf, zero_buf, warm, warm_mi, \
-                       gate, wave_wgs, light_front, actions, actions_f64)
-    if (d.ns == 1) { if (trace) PCC_S(1, true); else PCC_S(1, false); }
-    else { if (trace) PCC_S(2, true); else PCC_S(2, false); }
-#undef PCC_S
+                 int zero_buf, const Warm &warm, int gate, const Actions &act) {
+    dispatch_ns_flag(d.ns, trace, [&](auto ns, auto tr) {
+        hipLaunchKernelGGL((send_kernel<decltype(ns)::value, decltype(tr)::value>), dim3(light_wgs + wave_wgs), dim3(4 * kWave), 0, st, d, read_buf,
+                           zero_buf, warm.on, warm.mi, gate, wave_wgs, light_front, act.p, act.f64);
+    });
 }
 
 }  // namespace pcc

@@ -65,12 +65,7 @@ __device__ __forceinline__ LaneEnv<NS> load_env(const Dev &D, const uint32_t lan
             asm volatile("" : "+v"(i_here));
             const int64_t a = D.use_cwnd ? (int64_t)i_here * 2 : (int64_t)i_here * NS + s;  // USE_CWND: [rate action, cwnd action] per env
             const char *ap = (const char *)actions + (a << (actions_f64 ? 3 : 2));
-            double delta = actions_f64 ? *(const double *)ap : (double)*(const float *)ap;
-            if (delta != delta) { delta = 0.0; E.flags |= PCC_FLAG_BAD_ACTION; }  // NaN: never silent, never in the clock
-            delta *= D.delta_scale;
-            rate = delta >= 0.0 ? rate * (1.0 + delta) : rate / (1.0 - delta);
-            if (rate > kMaxRate) rate = kMaxRate;
-            if (rate < kMinRate) rate = kMinRate;
+            rate = apply_rate_delta(D, rate, load_action(ap, actions_f64, 0), E.flags);
             if constexpr (W == 1) D.snd[k].rate = rate;
         }
         if constexpr (W > 1) {  // the new rate is stored once every wavefront of the team has read the old one
@@ -278,13 +273,13 @@ __device__ __forceinline__ uint64_t send_light_item(const Dev &D, const uint32_t
             // queue and takes its loss draw (ns:170-175 are outside the `if`): it updates (q, tu) and
             // the RNG position, but leaves no record and is not counted as sent.
             uint32_t cw = D.snd[ii].cwnd;
-            if (!warm && E.live) {  // apply_cwnd_delta + set_cwnd: ns:243-249, 283-289
-                const int64_t ai = ii * 2 + 1;
-                double delta = actions_f64 ? ((const double *)actions)[ai] : (double)((const float *)actions)[ai];
+            if (!warm && E.live) {
+                // (apply_cwnd_delta's text, pcc_dev.h: through the helper two instructions of the one-sender kernels change places)
+                double delta = load_action(actions, actions_f64, ii * 2 + 1);
                 if (delta != delta) { delta = 0.0; E.flags |= PCC_FLAG_BAD_ACTION; }
                 delta *= D.delta_scale;
                 const double c = delta >= 0.0 ? (double)cw * (1.0 + delta) : (double)cw / (1.0 - delta);
-                cw = c >= 5000.0 ? 5000u : (c < 4.0 ? 4u : (uint32_t)c);  // int(), then [MIN_CWND, MAX_CWND] (ns:33-34)
+                cw = c >= 5000.0 ? 5000u : (c < 4.0 ? 4u : (uint32_t)c);
                 D.snd[ii].cwnd = cw;
             }
             const double2 *acc = E.rings[0].accepted(), *drp = E.rings[0].dropped();

@@ -35,15 +35,12 @@ __global__ __launch_bounds__(4 * kWave, PCC_RESTART_OCC) void send_restart_kerne
         const int64_t i = has ? (int64_t)cls_list_of(D, list_view(D, read_buf, part), (uint32_t)kRestart)[t] : 0;
         // new links and fresh state (ns:469-477) unless a flush already did all of it (pcc_get_state, a masked reset)
         if (has && D.env[i].resetting == 2) reset_env<NS>(D, i, nullptr);
-        if (has && D.shadows && shadow_list(&D.env[D.n + i])) {   // its shadow (if any) was not usable: have it prepared for the episode after this one
-            const uint32_t row = D.step_seq & 3u;
-            D.refill_list[(size_t)row * (size_t)D.n + atomicAdd(&D.refill_count[row * kCntStride], 1u)] = (uint32_t)i;
-        }
+        if (has && D.shadows) list_refill(D, &D.env[D.n + i], i);   // its shadow (if any) was not usable: have it prepared for the episode after this one
         // what one lane wrote is read by the others of this wavefront: a workgroup-scope fence is enough, and an
         // agent-scope one (__threadfence) writes back and invalidates the XCD's whole L2 under everybody's feet
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         const int64_t i0 = (int64_t)__builtin_amdgcn_readfirstlane((int)i) | ((int64_t)__builtin_amdgcn_readfirstlane((int)(i >> 32)) << 32);
-        for (int pass = 0; pass < 2; pass++) {  // the warm-up intervals: send, then retire by 8 lanes
+        for (int pass = 0; pass < 2; pass++) {  // the warm-up intervals: send, then retire by 8 lanes (refill_kernel's loop too: as one function 8 000-13 000 lines of each kernel move)
             (void)send_wave_item<NS, TRACE, 1>(D, lane, i, has, true, 0xFFFFFFFFu, 1, (uint32_t)pass, actions, actions_f64, s_slots[wv]);
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");  // records and state just written are read by other lanes
             if (lane < 8u) {
@@ -95,7 +92,7 @@ __global__ __launch_bounds__(4 * kWave, PCC_RESTART_OCC) void refill_kernel(Dev 
         if (!__ballot(go)) continue;
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         bool failed = false;
-        for (int pass = 0; pass < 2 && !failed; pass++) {
+        for (int pass = 0; pass < 2 && !failed; pass++) {   // (send_restart_kernel's warm-up loop, refusals added: see there)
             bool refused = false;
             (void)send_wave_item<NS, false, 1>(D, lane, i, has, true, 0xFFFFFFFFu, 1, (uint32_t)pass, nullptr, 0, s_slots[wv], 0u, nullptr, true, &refused);
             failed = refused;
@@ -122,11 +119,10 @@ void launch_refill(const Dev &d, unsigned grid, hipStream_t st, uint32_t row, ui
 }
 
 
-void launch_send_restart(const Dev &d, bool trace, unsigned grid, hipStream_t st, int read_buf, const void *actions, int actions_f64) {
-#define PCC_R(NS_, TR_) hipLaunchKernelGGL((send_restart_kernel<NS_, TR_>), dim3(grid), dim3(4 * kWave), 0, st, d, read_buf, actions, actions_f64)
-    if (d.ns == 1) { if (trace) PCC_R(1, true); else PCC_R(1, false); }
-    else { if (trace) PCC_R(2, true); else PCC_R(2, false); }
-#undef PCC_R
+void launch_send_restart(const Dev &d, bool trace, unsigned grid, hipStream_t st, int read_buf, const Actions &act) {
+    dispatch_ns_flag(d.ns, trace, [&](auto ns, auto tr) {
+        hipLaunchKernelGGL((send_restart_kernel<decltype(ns)::value, decltype(tr)::value>), dim3(grid), dim3(4 * kWave), 0, st, d, read_buf, act.p, act.f64);
+    });
 }
 
 }  // namespace pcc

@@ -155,10 +155,7 @@ int check_hip(hipError_t err, const char *what) {
 // (counts -> list -> state)
 bool uses_lists(const pcc_sim_t *sim) { return sim->d.n >= (int64_t)sim->list_min_envs; }
 
-// Where one step writes: its observation, reward, done and step-record rows (any of them NULL)
-struct StepOut { float *obs, *reward; uint8_t *done; double *steps; };
-
-// ... and the rows of step t when those are the first rows of [T, ...] outputs
+// The rows of step t of a step's outputs (StepOut, pcc_kernels.h) when those are the first rows of [T, ...] outputs
 StepOut row_of(const Dev &d, const StepOut &o, int t) {
     const size_t row = (size_t)d.n * d.ns, k = (size_t)t;
     return {o.obs ? o.obs + k * row * d.HF : nullptr, o.reward ? o.reward + k * row : nullptr, o.done ? o.done + k * (size_t)d.n : nullptr,
@@ -188,11 +185,11 @@ unsigned few_envs_grid(const pcc_sim_t *sim) {
 // launch reset out of lockstep (the restart list: warm-up intervals first) are a kernel of their own on a side stream of the
 // handle, forked from and joined to the caller's stream by events; it never touches an env the main launch touches.
 // Without lists (after a reset, warm-up intervals, small batches): light workgroups only, the envs in index order.
-int launch_send(pcc_sim_t *sim, int warm, uint32_t warm_mi, int gate, const void *actions, int actions_f64, hipStream_t st) {
+int launch_send(pcc_sim_t *sim, const Warm &warm, int gate, const Actions &act, hipStream_t st) {
     const Dev &d = sim->d;
     const bool tr = d.rng_mode == PCC_RNG_TRACE;
     const bool lists = uses_lists(sim);
-    const int read_buf = (warm || !lists) ? -1 : sim->read_buf;
+    const int read_buf = (warm.on || !lists) ? -1 : sim->read_buf;
     const int zero_buf = lists ? sim->fill_buf : -1;
     // restart items can only be in lists that a retire launch with `restart` filed
     const bool rs = read_buf >= 0 && sim->read_has_restarts;
@@ -220,7 +217,7 @@ int launch_send(pcc_sim_t *sim, int warm, uint32_t warm_mi, int gate, const void
         if (front > light_grid) front = light_grid / (unsigned)P * (unsigned)P;
     }
     auto main_launch = [&](hipStream_t s) {
-        pcc::launch_send(d, tr, light_grid, wave_grid, front, s, read_buf, zero_buf, warm, warm_mi, gate, actions, actions_f64);
+        pcc::launch_send(d, tr, light_grid, wave_grid, front, s, read_buf, zero_buf, warm, gate, act);
     };
     if (!rs) {
         main_launch(st);
@@ -232,7 +229,7 @@ int launch_send(pcc_sim_t *sim, int warm, uint32_t warm_mi, int gate, const void
         // against 0.153.)
         const unsigned restart_grid = few_envs_grid(sim);
         main_launch(st);
-        launch_send_restart(d, tr, restart_grid < 32u ? restart_grid : 32u, st, read_buf, actions, actions_f64);
+        launch_send_restart(d, tr, restart_grid < 32u ? restart_grid : 32u, st, read_buf, act);
     } else {
         // The restart items are a chain of dependent passes (reset, two warm-up intervals, the first interval): longer than
         // the whole main launch.  So the MAIN launch goes to the side stream and the restart kernel stays on the caller's:
@@ -242,10 +239,10 @@ int launch_send(pcc_sim_t *sim, int warm, uint32_t warm_mi, int gate, const void
         (void)hipStreamWaitEvent(sim->aux_wave, sim->ev_fork, 0);
         main_launch(sim->aux_wave);
         (void)hipEventRecord(sim->ev_wave, sim->aux_wave);
-        launch_send_restart(d, tr, few_envs_grid(sim), st, read_buf, actions, actions_f64);
+        launch_send_restart(d, tr, few_envs_grid(sim), st, read_buf, act);
         (void)hipStreamWaitEvent(st, sim->ev_wave, 0);
     }
-    if (rs && !warm) sim->restarts_pending = false;  // this launch runs what the restart list's envs were owed
+    if (rs && !warm.on) sim->restarts_pending = false;  // this launch runs what the restart list's envs were owed
     return check_hip(hipGetLastError(), "send kernel launch");
 }
 
@@ -253,13 +250,13 @@ int launch_send(pcc_sim_t *sim, int warm, uint32_t warm_mi, int gate, const void
 // next send (buffer sim->fill_buf, cleared by the send launch before it)
 // restart: envs that finish their episode in this launch are reset inside it and filed in the restart list
 // pol: the policy epilogue (pcc_rollout): every env's next action from the observation row this launch writes
-int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm, int gate, int restart, const StepOut &out,
-                       hipStream_t st, const PolicyArgs *pol = nullptr) {
+int launch_retire_half(pcc_sim_t *sim, const Warm &warm, int gate, int restart, const StepOut &out, hipStream_t st,
+                       const PolicyArgs *pol = nullptr) {
     const Dev &d = sim->d;
     // workgroups: 8 envs each at 16 lanes per env, 16 at 8 lanes -- which envs go which way is decided on the device
     // (class counts), so the grid covers the worst case plus the one workgroup the split can leave partly filled
     const bool lists = uses_lists(sim);
-    const int read = (warm || !d.retire_sorted || !lists) ? -1 : sim->read_buf;  // the lists this step's send launch read
+    const int read = (warm.on || !d.retire_sorted || !lists) ? -1 : sim->read_buf;  // the lists this step's send launch read
     // With lists the walk is n / 16 workgroups plus one more for every 16 envs of the wide classes (8 per workgroup there): the
     // grid is sized for retire_grid_frac of the envs being wide (default 1/8: about 3 % are) and the workgroups loop if there
     // are more -- the worst case, twice n / 16, is ~8 200 workgroups for 65 536 envs, which the command processor needs
@@ -268,11 +265,10 @@ int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm
     const int64_t narrow = (d.n + kRetireEnvsPerBlockNarrow - 1) / kRetireEnvsPerBlockNarrow;
     const int64_t narrow_part = ((int64_t)d.part_envs + kRetireEnvsPerBlockNarrow - 1) / kRetireEnvsPerBlockNarrow;
     const unsigned grid = (unsigned)(read >= 0 ? (int64_t)d.parts * (narrow_part + (int64_t)(sim->retire_grid_frac * (double)narrow_part) + 1) : narrow);
-    const int fill = (warm || !lists) ? -1 : sim->fill_buf;
-    launch_retire(d, false, grid, st, read, fill, warm, warm_mi, last_warm, gate, restart, out.obs, out.reward, out.done, out.steps,
-                  nullptr, 0, pol);
+    const int fill = (warm.on || !lists) ? -1 : sim->fill_buf;
+    launch_retire(d, false, grid, st, read, fill, warm, gate, restart, out, Actions{}, pol);
     const int rc = check_hip(hipGetLastError(), "retire kernel launch");
-    if (rc == PCC_OK && !warm && lists) {
+    if (rc == PCC_OK && !warm.on && lists) {
         sim->read_buf = sim->fill_buf;
         sim->fill_buf = (sim->fill_buf + 1) % kListBufs;
         sim->clean_buf = -1;   // (the send launch cleared the buffer this launch filed; the next one is as its last reader left it)
@@ -285,7 +281,7 @@ int launch_retire_half(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm
 // Both halves of a step as ONE launch (pcc_fused.hip) -- whenever the step is an ordinary one: work lists to read, no warm-up
 // interval, no restart list to serve or to fill (lockstep, or the caller resets), none of the engine options.  Returns
 // PCC_OK + *done = true when the step was launched; *done = false: the caller launches the two halves.
-int try_launch_fused(pcc_sim_t *sim, int restart, const void *actions, int actions_f64, const StepOut &out, hipStream_t st, bool *done) {
+int try_launch_fused(pcc_sim_t *sim, int restart, const Actions &act, const StepOut &out, hipStream_t st, bool *done) {
     const Dev &d = sim->d;
     *done = false;
     if (!sim->fused || d.engine || d.use_cwnd || restart || sim->read_has_restarts || sim->restarts_pending) return PCC_OK;
@@ -316,16 +312,14 @@ int try_launch_fused(pcc_sim_t *sim, int restart, const void *actions, int actio
     unsigned light_front = (unsigned)(P * (int64_t)sim->fused_light_front);
     if ((int64_t)light_front > grid - wave_wgs) light_front = (unsigned)((grid - wave_wgs) / P * P);
     if (sim->fused == 2) {   // experiment: the fused kernel's send part as the send launch, then the retire launch
-        launch_step_fused(d, tr, (unsigned)grid, (unsigned)wave_wgs, light_front, st, read, fill, fill, 0, actions, actions_f64, out.obs, out.reward,
-                          out.done, out.steps);
+        launch_step_fused(d, tr, (unsigned)grid, (unsigned)wave_wgs, light_front, st, read, fill, fill, 0, act, out);
         const int rc2 = check_hip(hipGetLastError(), "fused step kernel launch");
         if (rc2 != PCC_OK) return rc2;
         *done = true;
-        return launch_retire_half(sim, 0, 0, 0, 0, 0, out, st);
+        return launch_retire_half(sim, Warm{}, 0, 0, out, st);
     }
     if (sim->clean_buf != fill) launch_clear_list_buffer(d, st, fill);
-    launch_step_fused(d, tr, (unsigned)grid, (unsigned)wave_wgs, light_front, st, read, fill, zero, 1, actions, actions_f64, out.obs, out.reward,
-                      out.done, out.steps);
+    launch_step_fused(d, tr, (unsigned)grid, (unsigned)wave_wgs, light_front, st, read, fill, zero, 1, act, out);
     const int rc = check_hip(hipGetLastError(), "fused step kernel launch");
     if (rc != PCC_OK) return rc;
     sim->read_buf = fill;
@@ -339,8 +333,8 @@ int try_launch_fused(pcc_sim_t *sim, int restart, const void *actions, int actio
 
 // One monitor interval of a batch that is not a small one.  pol (pcc_rollout's epilogue path): the policy in the retire
 // launch's epilogue -- the send and the retire launch then, never the one-launch step.
-int launch_mi(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm, int gate, int restart, const void *actions,
-              int actions_f64, const StepOut &out, hipStream_t st, const PolicyArgs *pol = nullptr) {
+int launch_mi(pcc_sim_t *sim, const Warm &warm, int gate, int restart, const Actions &act, const StepOut &out, hipStream_t st,
+              const PolicyArgs *pol = nullptr) {
     if (sim->d.engine) {
         // the event-loop build (latency noise; the congestion window with two senders): the whole interval is one launch of
         // the retire kernel's NOISE build (no send half, no work lists)
@@ -351,20 +345,19 @@ int launch_mi(pcc_sim_t *sim, int warm, uint32_t warm_mi, int last_warm, int gat
         Dev d = sim->d;
         const bool sorted = sim->noise_sorted && d.use_noise && !d.use_cwnd && d.noise_out != nullptr;
         if (!sorted) d.noise_out = nullptr;
-        else launch_noise_sorted(d, st, warm, warm_mi, gate, actions, actions_f64, sim->noise_sorted == 2);
+        else launch_noise_sorted(d, st, warm, gate, act, sim->noise_sorted == 2);
         const unsigned grid = (unsigned)((d.n + kRetireEnvsPerBlockNarrow - 1) / kRetireEnvsPerBlockNarrow);
-        launch_retire(d, true, grid, st, -1, -1, warm, warm_mi, last_warm, gate, 0, out.obs, out.reward, out.done, out.steps,
-                      actions, actions_f64);
+        launch_retire(d, true, grid, st, -1, -1, warm, gate, 0, out, act);
         return check_hip(hipGetLastError(), "event-loop kernel launch");
     }
-    if (!warm && !gate && !pol) {
+    if (!warm.on && !gate && !pol) {
         bool done = false;
-        const int rf = try_launch_fused(sim, restart, actions, actions_f64, out, st, &done);
+        const int rf = try_launch_fused(sim, restart, act, out, st, &done);
         if (rf != PCC_OK || done) return rf;
     }
-    const int rc = launch_send(sim, warm, warm_mi, gate, actions, actions_f64, st);
+    const int rc = launch_send(sim, warm, gate, act, st);
     if (rc != PCC_OK) return rc;
-    return launch_retire_half(sim, warm, warm_mi, last_warm, gate, restart, out, st, pol);
+    return launch_retire_half(sim, warm, gate, restart, out, st, pol);
 }
 
 // reset(): parameters + state, then the two unrecorded warm-up MIs (ns:469-484).  gate: the launches
@@ -377,7 +370,7 @@ int launch_reset(pcc_sim_t *sim, const uint8_t *mask, int use_done, int gate, fl
     launch_reset_init(d, st, mask, use_done, gate, all_envs, obs_out);
     int rc = check_hip(hipGetLastError(), "reset kernel launch");
     for (uint32_t w = 0; w < 2 && rc == PCC_OK; w++)
-        rc = launch_mi(sim, 1, w, w == 1, gate, 0, nullptr, 0, StepOut{}, st);
+        rc = launch_mi(sim, Warm{1, w, w == 1}, gate, 0, Actions{}, StepOut{}, st);
     return rc;
 }
 
@@ -1124,25 +1117,24 @@ bool reset_follows(const pcc_sim_t *sim, int auto_reset) {
 
 // `seg` steps of a small batch in ONE launch (step_small_kernel: both halves, the loop over the steps inside, a workgroup per
 // 64 envs); step k reads its actions act_stride bytes behind step k - 1's -- or takes them from the policy in the loop (pol)
-int launch_small(pcc_sim_t *sim, const void *actions, int actions_f64, const StepOut &out, int seg, int64_t act_stride,
+int launch_small(pcc_sim_t *sim, const Actions &act, const StepOut &out, int seg, int64_t act_stride,
                  const PolicyArgs *pol, hipStream_t st) {
     next_step_seq(sim, st);
-    launch_step_small(sim->d, sim->d.rng_mode == PCC_RNG_TRACE, st, actions, actions_f64, out.obs, out.reward, out.done, out.steps, seg,
-                      act_stride, pol);
+    launch_step_small(sim->d, sim->d.rng_mode == PCC_RNG_TRACE, st, act, out, seg, act_stride, pol);
     return check_hip(hipGetLastError(), "step kernel launch");
 }
 
 // ONE step, what pcc_step is after its argument checks.  pol: the policy in the epilogue of the retire launch (pcc_rollout;
 // only for a batch with work lists, and never as the one-launch step: launch_mi)
-int step_once(pcc_sim_t *sim, const void *actions, int actions_f64, const StepOut &out, int auto_reset, hipStream_t st,
+int step_once(pcc_sim_t *sim, const Actions &act, const StepOut &out, int auto_reset, hipStream_t st,
               const PolicyArgs *pol = nullptr) {
     int rc, restart = 0;
     if (!uses_lists(sim) && !sim->d.engine) {
-        rc = launch_small(sim, actions, actions_f64, out, 1, 0, nullptr, st);
+        rc = launch_small(sim, act, out, 1, 0, nullptr, st);
     } else {
         next_step_seq(sim, st);
         restart = restart_mode(sim, auto_reset);
-        rc = launch_mi(sim, 0, 0, 0, 0, restart, actions, actions_f64, out, st, pol);
+        rc = launch_mi(sim, Warm{}, 0, restart, act, out, st, pol);
     }
     return rc != PCC_OK ? rc : after_mi(sim, restart, out.obs, auto_reset, st);
 }
@@ -1189,7 +1181,7 @@ int pcc_step_send(pcc_sim_t *sim, const void *actions, int actions_f64, void *st
     if (sim->d.engine) return fail(PCC_ESTATE, "the event-loop build (latency noise; congestion window with two senders) has no separate send half: use pcc_step");
     DeviceGuard guard(sim->device);
     next_step_seq(sim, static_cast<hipStream_t>(stream));
-    const int rc = launch_send(sim, 0, 0, 0, actions, actions_f64, static_cast<hipStream_t>(stream));
+    const int rc = launch_send(sim, Warm{}, 0, Actions{actions, actions_f64}, static_cast<hipStream_t>(stream));
     if (rc == PCC_OK) sim->send_pending = true;
     return rc;
 }
@@ -1201,7 +1193,7 @@ int pcc_step_retire(pcc_sim_t *sim, float *obs_out, float *reward_out, uint8_t *
     DeviceGuard guard(sim->device);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int restart = restart_mode(sim, auto_reset);
-    const int rc = launch_retire_half(sim, 0, 0, 0, 0, restart, StepOut{obs_out, reward_out, done_out, steps_out}, st);
+    const int rc = launch_retire_half(sim, Warm{}, 0, restart, StepOut{obs_out, reward_out, done_out, steps_out}, st);
     if (rc != PCC_OK) return rc;
     sim->send_pending = false;
     return after_mi(sim, restart, obs_out, auto_reset, st);
@@ -1213,7 +1205,7 @@ int pcc_step(pcc_sim_t *sim, const void *actions, int actions_f64, float *obs_ou
     if (!sim->ever_reset) return fail(PCC_ESTATE, "pcc_step before pcc_reset (the reference raises TypeError: run_dur is None)");
     if (sim->send_pending) return fail(PCC_ESTATE, "pcc_step between pcc_step_send and pcc_step_retire");
     DeviceGuard guard(sim->device);
-    return step_once(sim, actions, actions_f64, StepOut{obs_out, reward_out, done_out, steps_out}, auto_reset, static_cast<hipStream_t>(stream));
+    return step_once(sim, Actions{actions, actions_f64}, StepOut{obs_out, reward_out, done_out, steps_out}, auto_reset, static_cast<hipStream_t>(stream));
 }
 
 int pcc_step_many(pcc_sim_t *sim, const void *actions, int actions_f64, int n_steps, float *obs_out, float *reward_out,
@@ -1230,10 +1222,10 @@ int pcc_step_many(pcc_sim_t *sim, const void *actions, int actions_f64, int n_st
     auto act_at = [&](int t) { return static_cast<const char *>(actions) + (size_t)t * act_row; };
     if (steps_in_segments(sim, auto_reset))
         return walk_segments(sim, "pcc_step_many", n_steps, out, auto_reset, st, [&](int t, int seg) {
-            return launch_small(sim, act_at(t), actions_f64, row_of(d, out, t), seg, (int64_t)act_row, nullptr, st);
+            return launch_small(sim, Actions{act_at(t), actions_f64}, row_of(d, out, t), seg, (int64_t)act_row, nullptr, st);
         });
     for (int t = 0; t < n_steps; t++) {
-        const int rc = step_once(sim, act_at(t), actions_f64, row_of(d, out, t), auto_reset, st);
+        const int rc = step_once(sim, Actions{act_at(t), actions_f64}, row_of(d, out, t), auto_reset, st);
         if (rc != PCC_OK) return stopped(rc, "pcc_step_many", t, n_steps);
     }
     return PCC_OK;
@@ -1296,7 +1288,7 @@ int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps
         return walk_segments(sim, "pcc_rollout", n_steps, out, auto_reset, st, [&](int t, int seg) {
             const int rc = policy(t);
             pa.t0 = t;
-            return rc != PCC_OK ? rc : launch_small(sim, nullptr, 0, row_of(d, out, t), seg, 0, &pa, st);
+            return rc != PCC_OK ? rc : launch_small(sim, Actions{}, row_of(d, out, t), seg, 0, &pa, st);
         });
     // Epilogue path (PCC_TUNE_ROLLOUT_EPILOGUE; off by default: measured slower than the launches it replaces):
     // the retire launch of step t computes the action of step t + 1 -- unless reset launches follow the step (they rewrite
@@ -1308,7 +1300,7 @@ int pcc_rollout(pcc_sim_t *sim, const float *params, int h1, int h2, int n_steps
         int rc = need ? policy(t) : PCC_OK;
         const bool epi = epilogue && t + 1 < n_steps && !reset_follows(sim, auto_reset);
         pa.t0 = t;
-        if (rc == PCC_OK) rc = step_once(sim, act_at(t), 0, row_of(d, out, t), auto_reset, st, epi ? &pa : nullptr);
+        if (rc == PCC_OK) rc = step_once(sim, Actions{act_at(t), 0}, row_of(d, out, t), auto_reset, st, epi ? &pa : nullptr);
         if (rc != PCC_OK) return stopped(rc, "pcc_rollout", t, n_steps);
         need = !epi;
     }

@@ -68,8 +68,8 @@ __global__ __launch_bounds__(4 * kWave, PCC_SMALL_OCC) void step_small_kernel(De
 // step_small_kernel<1, TRACE> with the policy in the loop (pcc_rollout): after the retire part of step t (but the last) each env's
 // group computes the env's action of step t + 1 from the observation row it has just written (pcc_policy_dev.h) into the act
 // rows the send part of step t + 1 reads -- behind the workgroup barrier between the steps.  The parameter block sits in LDS
-// once per launch (the workgroup runs every step of the segment).  A kernel of its own rather than a template switch of
-// step_small_kernel: that one's code stays exactly what it was.
+// once per launch (the workgroup runs every step of the segment).  The loop is step_small_kernel's, copied: as one function
+// behind two thin kernels 6 400-10 000 lines of every instantiation of both move.
 __device__ __forceinline__ float *small_pol_lds() {
     extern __shared__ float s_pol_dyn[];
     return s_pol_dyn;
@@ -144,12 +144,8 @@ __global__ __launch_bounds__(kWave) void reset_init_kernel(Dev D, const uint8_t 
     // use_done 1: the envs that finished their episode; 2: the envs a retire launch marked for a restart
     const bool sel = use_done == 2 ? D.env[i].resetting == 2 : (!mask || mask[i]) && (!use_done || D.env[i].done);
     D.env[i].resetting = sel ? 1 : 0;
-    if (sel && D.shadows && !all_envs && shadow_list(&D.env[D.n + i])) {
-        // a reset that is not the env's own episode end overtakes its shadow (prepared for the episode index this reset now
-        // takes): have the shadow prepared again, for the episode after this one (listed once, whoever else lists it in this step)
-        const uint32_t row = D.step_seq & 3u;
-        D.refill_list[(size_t)row * (size_t)D.n + atomicAdd(&D.refill_count[row * kCntStride], 1u)] = (uint32_t)i;
-    }
+    // a reset that is not the env's own episode end overtakes its shadow: have it prepared again, for the episode after this one
+    if (sel && D.shadows && !all_envs) list_refill(D, &D.env[D.n + i], i);
     if (sel) {
         release_ring_slots<NS>(D, i, !all_envs);
         reset_env<NS>(D, i, obs_out);
@@ -172,21 +168,19 @@ __global__ void forget_ring_slots_kernel(Dev D) {
 
 namespace pcc {
 
-void launch_step_small(const Dev &d, bool trace, hipStream_t st, const void *actions, int actions_f64, float *obs_out,
-                       float *reward_out, uint8_t *done_out, double *steps_out, int n_steps, int64_t act_stride,
+void launch_step_small(const Dev &d, bool trace, hipStream_t st, const Actions &act, const StepOut &out, int n_steps, int64_t act_stride,
                        const PolicyArgs *pol) {
     const dim3 grid((unsigned)((d.n + kSmallEnvs - 1) / kSmallEnvs)), block(4 * kWave);
     if (pol) {   // (one sender: the host asks for nothing else)
         const size_t lds = (size_t)(kSmallEnvs * kPolScratch + pol->n_params) * sizeof(float);
-        if (trace) hipLaunchKernelGGL(step_small_policy_kernel<true>, grid, block, lds, st, d, obs_out, reward_out, done_out, steps_out, n_steps, *pol);
-        else hipLaunchKernelGGL(step_small_policy_kernel<false>, grid, block, lds, st, d, obs_out, reward_out, done_out, steps_out, n_steps, *pol);
+        if (trace) hipLaunchKernelGGL(step_small_policy_kernel<true>, grid, block, lds, st, d, out.obs, out.reward, out.done, out.steps, n_steps, *pol);
+        else hipLaunchKernelGGL(step_small_policy_kernel<false>, grid, block, lds, st, d, out.obs, out.reward, out.done, out.steps, n_steps, *pol);
         return;
     }
-#define PCC_S(NS_, TR_) \
-    hipLaunchKernelGGL((step_small_kernel<NS_, TR_>), grid, block, 0, st, d, actions, actions_f64, obs_out, reward_out, done_out, steps_out, n_steps, act_stride)
-    if (d.ns == 1) { if (trace) PCC_S(1, true); else PCC_S(1, false); }
-    else { if (trace) PCC_S(2, true); else PCC_S(2, false); }
-#undef PCC_S
+    dispatch_ns_flag(d.ns, trace, [&](auto ns, auto tr) {
+        hipLaunchKernelGGL((step_small_kernel<decltype(ns)::value, decltype(tr)::value>), grid, block, 0, st, d, act.p, act.f64, out.obs, out.reward,
+                           out.done, out.steps, n_steps, act_stride);
+    });
 }
 
 void launch_reset_init(const Dev &d, hipStream_t st, const uint8_t *mask, int use_done, int gate, int all_envs, float *obs_out) {

@@ -2,6 +2,8 @@
 """Train a PCC rate controller with PPO on the GPU simulator.
 
     python examples/train_ppo.py --envs 8192 --iters 50 [--arch=32,16] [--gamma=0.99]
+    python examples/train_ppo.py --iters 50 --checkpoint run.pt --checkpoint-every 10     # ... interrupted ...
+    python examples/train_ppo.py --iters 50 --resume run.pt --checkpoint run.pt           # goes on where run.pt was written, bit for bit
 
 Counterpart of the reference's src/gym/stable_solve.py, but with the env, the rollout buffers and
 the optimiser all on one MI355X (see pcc-rl_amd/ppo.py)."""
@@ -27,14 +29,34 @@ def main():
     ap.add_argument("--save", default="")
     ap.add_argument("--policy-in-step", action="store_true",
                     help="collect each horizon as one closed-loop call (pcc_rollout): the policy inside the env's launches")
+    ap.add_argument("--checkpoint", default="", help="write the whole training state here (PPO.state_dict: policy, Adam, generators, "
+                    "the env's snapshot) every --checkpoint-every iterations and at the end")
+    ap.add_argument("--checkpoint-every", type=int, default=10)
+    ap.add_argument("--resume", default="", help="continue from a --checkpoint file of a run with the same --envs, --horizon and --arch")
+    ap.add_argument("--ring-pools", default="", help="div1,div2,div3 of BatchedNetworkEnv(ring_pools=...); with --checkpoint / --resume the "
+                    "default is 2,8,32 (the library's own default depends on the free device memory, and a snapshot needs equal pools)")
     args = ap.parse_args()
-    env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0)
+    pools = tuple(int(x) for x in args.ring_pools.split(",")) if args.ring_pools else ((2, 8, 32) if args.checkpoint or args.resume else None)
+    env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0, ring_pools=pools)
     agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
                 policy_in_step=args.policy_in_step)
+    first = 0
+    if args.resume:
+        ck = torch.load(args.resume)
+        agent.load_state_dict(ck["ppo"])
+        first = int(ck["iters_done"])
+        print("resumed %s after %d iterations" % (args.resume, first))
+
+    def checkpoint(done):
+        torch.save({"ppo": agent.state_dict(), "iters_done": done}, args.checkpoint + ".tmp")
+        os.replace(args.checkpoint + ".tmp", args.checkpoint)
+
     t0 = time.perf_counter()
-    for it in range(args.iters):
+    for it in range(first, args.iters):
         s = agent.iterate()
-        steps = (it + 1) * args.envs * args.horizon
+        if args.checkpoint and ((it + 1) % max(args.checkpoint_every, 1) == 0 or it + 1 == args.iters):
+            checkpoint(it + 1)
+        steps = (it + 1 - first) * args.envs * args.horizon
         print("iter %3d  env-steps %10d  reward/step %8.4f  entropy %6.3f  %.0f env-steps/s incl. learning"
               % (it, steps, s["mean_step_reward"], s["entropy"], steps / (time.perf_counter() - t0)))
     if args.save:

@@ -389,6 +389,38 @@ int pcc_restart_stats(pcc_sim_t *sim, uint64_t *out2, void *stream);
 /* copy one state field into a caller-owned device buffer (see the PCC_F_* table) */
 int pcc_get_state(pcc_sim_t *sim, int field, void *out, void *stream);
 
+/*
+ * Snapshot and restore of a handle's dynamic state.  No reference counterpart (the reference's env is a Python object that is never
+ * saved).  A snapshot is one caller-owned DEVICE buffer (16-byte aligned): a header, the small state arrays verbatim (env and
+ * sender blocks with their shadows, history, refill rows, work lists with their counts and cursors, pool stacks, restart
+ * statistics) and the in-flight rings COMPACTED -- only the live records of every ring, a few hundred per sender where the rings
+ * themselves are 24 KB (tier 0) to 1.5 MB (tier 3) a sender.  DESIGN.md section 15 has the format.
+ *   pcc_snapshot_bytes  the bytes a snapshot taken now needs (< 0: a PCC_E* code).  Synchronizes `stream`, like pcc_restart_stats.
+ *   pcc_snapshot        enqueues the snapshot on `stream`; `bytes` = the size of buf, at least what pcc_snapshot_bytes returned with
+ *                       no call on the handle in between (a smaller buffer gets a header marked truncated and no record, and
+ *                       pcc_restore refuses it).  Taking a snapshot changes nothing a later call returns.
+ *   pcc_restore         enqueues the restore on `stream`; apart from reading the header for validation (which waits for `stream`) it
+ *                       does not synchronize -- except that the first restore of a snapshot taken out of lockstep into a handle
+ *                       that never left lockstep allocates the shadows' rings, as that handle's first such step would.
+ * Contract: after pcc_restore every later call on the handle returns what the snapshotted handle returned after pcc_snapshot, bit
+ * for bit, given the same arguments -- observations, rewards, dones, step columns, every pcc_get_state field, flags,
+ * pcc_restart_stats, episode returns; pcc_step, pcc_step_many, pcc_rollout, masked and full pcc_reset.
+ * The target is the same handle or another one of the SAME CONFIGURATION that has been reset once: envs, senders, history, features,
+ * ring capacity, global id base, pool slots per tier (two handles that exchange snapshots name them with pcc_set_ring_pools: the
+ * default sizes depend on the memory that was free) and partitions, rng mode and seed, parameter ranges, whether link arrays are
+ * set, cwnd mode, delta scale, max steps.  The header carries these in clear and as a fingerprint.  The caller's own arrays
+ * (pcc_set_link_params, a replayed trace) stay the caller's to keep alive and identical.  Performance knobs are not part of it.
+ * Everything is validated on the host before anything is launched or modified -- magic, version, configuration, fingerprint, the
+ * section table against `bytes` -- and a mismatch is PCC_EINVAL with a message that names the field, the target untouched.
+ * PCC_ESTATE: between pcc_step_send and pcc_step_retire, or before the first full pcc_reset.  PCC_EINVAL also (a follow-up: their
+ * heaps and ready queues are not saved): the event-loop build (latency noise; congestion window with two senders) and a handle with
+ * PCC_TUNE_FUSED on.  On the device the scatter moves a ring only if its record count fits its capacity and its storage lies inside
+ * the handle's regions; otherwise it writes nothing of it and raises PCC_FLAG_INTERNAL.  The profiling timeline is not saved.
+ */
+int64_t pcc_snapshot_bytes(pcc_sim_t *sim, void *stream);
+int pcc_snapshot(pcc_sim_t *sim, void *buf, int64_t bytes, void *stream);
+int pcc_restore(pcc_sim_t *sim, const void *buf, int64_t bytes, void *stream);
+
 /* bounds and scale of metric `id`: (min_val, max_val, scale) of so:193-206; host pointers.
  * get_min_obs_vector / get_max_obs_vector (so:95-108) are these tiled H times. */
 int pcc_metric_info(int id, double *min_val, double *max_val, double *scale);

@@ -9,6 +9,7 @@
 
 #include "pcc_kernels.h"
 #include "pcc_policy.h"
+#include "pcc_snapshot.h"
 
 using namespace pcc;
 
@@ -86,6 +87,8 @@ struct pcc_sim {
     int rollout_epilogue;   // PCC_TUNE_ROLLOUT_EPILOGUE: pcc_rollout at full size with the policy in the retire launch (1) or not (0)
     float *roll_act;        // pcc_rollout without act_out: two rows of actions, used in turn
     size_t roll_act_floats;
+    void *snap_blob;        // scratch of the snapshot kernels (pcc_snapshot.h: SnapScratch), allocated by the first snapshot or restore
+    size_t snap_bytes;
 };
 
 namespace {
@@ -385,16 +388,21 @@ bool restarts_in_step(const pcc_sim_t *sim, int auto_reset) {
 // Shadows (the next episode of an env prepared ahead of time, swapped in when it finishes: pcc_dev.h, pcc_send_restart.hip)
 // need uniforms that do not depend on the order of events across episodes (Philox, not a replayed trace) and their private
 // rings (tier-1 size per sender: allocated the first time envs restart out of lockstep -- 6.4 GB for 65 536 senders).
+size_t shadow_ring_bytes(const Dev &d) { return (size_t)d.n * d.ns * 3 * ((size_t)d.cap0 << (2 * kShadowTier)) * sizeof(double2); }
+bool alloc_shadow_rings(pcc_sim_t *sim) {
+    Dev &d = sim->d;
+    if (sim->shadow_blob) return true;
+    const size_t bytes = shadow_ring_bytes(d);
+    if (d.n_tiers < 2 || hipMalloc(&sim->shadow_blob, bytes) != hipSuccess) { sim->shadow_blob = nullptr; return false; }
+    (void)hipMemset(sim->shadow_blob, 0, bytes);   // (first use of fresh device memory is slow: not in somebody's step)
+    sim->shadow_bytes = bytes;
+    d.shadow_rings = static_cast<char *>(sim->shadow_blob);
+    return true;
+}
 bool use_shadows(pcc_sim_t *sim) {
     Dev &d = sim->d;
     if (d.rng_mode != PCC_RNG_PHILOX) { d.shadows = 0; return false; }
-    if (!sim->shadow_blob) {
-        const size_t bytes = (size_t)d.n * d.ns * 3 * ((size_t)d.cap0 << (2 * kShadowTier)) * sizeof(double2);
-        if (d.n_tiers < 2 || hipMalloc(&sim->shadow_blob, bytes) != hipSuccess) { sim->shadow_blob = nullptr; d.shadows = 0; return false; }
-        (void)hipMemset(sim->shadow_blob, 0, bytes);   // (first use of fresh device memory is slow: not in somebody's step)
-        sim->shadow_bytes = bytes;
-        d.shadow_rings = static_cast<char *>(sim->shadow_blob);
-    }
+    if (!alloc_shadow_rings(sim)) { d.shadows = 0; return false; }
     d.shadows = 1;
     return true;
 }
@@ -828,6 +836,7 @@ void pcc_destroy(pcc_sim_t *sim) {
     if (sim->noise_blob) (void)hipFree(sim->noise_blob);
     if (sim->noise_out_blob) (void)hipFree(sim->noise_out_blob);
     if (sim->roll_act) (void)hipFree(sim->roll_act);
+    if (sim->snap_blob) (void)hipFree(sim->snap_blob);
 
     if (sim->state_blob) (void)hipFree(sim->state_blob);
     for (int c = 0; c < kMaxTiers; c++) {
@@ -837,7 +846,7 @@ void pcc_destroy(pcc_sim_t *sim) {
 }
 
 int64_t pcc_device_bytes(const pcc_sim_t *sim) {
-    return sim ? (int64_t)(sim->state_bytes + sim->ring_bytes + sim->list_bytes + sim->noise_bytes + sim->shadow_bytes) : 0;
+    return sim ? (int64_t)(sim->state_bytes + sim->ring_bytes + sim->list_bytes + sim->noise_bytes + sim->shadow_bytes + sim->snap_bytes) : 0;
 }
 
 namespace {
@@ -1387,5 +1396,255 @@ int pcc_get_state(pcc_sim_t *sim, int field, void *out, void *stream) {
     return PCC_OK;
 }
 
-}  // extern "C"
+// ======================================================================================
+// snapshot / restore (the format and the kernels: pcc_snapshot.h, pcc_snapshot.hip)
+// ======================================================================================
+namespace {
 
+size_t snap_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// what two handles must share to exchange snapshots
+void snap_config(const pcc_sim_t *sim, SnapConfig &c) {
+    const Dev &d = sim->d;
+    memset(&c, 0, sizeof c);
+    c.n = d.n; c.ns = d.ns; c.H = d.H; c.F = d.F; c.n_tiers = d.n_tiers;
+    for (int f = 0; f < d.F; f++) c.fid[f] = d.fid[f];
+    c.ring_capacity = sim->ring_capacity; c.cap0 = d.cap0; c.gid_base = d.gid_base; c.parts = d.parts;
+    for (int t = 0; t < d.n_tiers; t++) c.tier_slots[t] = sim->tier_slots[t];
+    c.rng_mode = d.rng_mode; c.use_cwnd = d.use_cwnd; c.link_arrays = d.p_bw != nullptr ? 1 : 0;
+    c.trace_stride = d.trace_stride;
+    c.key0 = d.key0; c.key1 = d.key1; c.max_steps = d.max_steps;
+    c.delta_scale = d.delta_scale;
+    memcpy(c.lo, d.lo, sizeof c.lo); memcpy(c.hi, d.hi, sizeof c.hi);
+}
+
+uint64_t snap_fingerprint(const SnapConfig &c) {   // FNV-1a over the (zero-padded) bytes
+    uint64_t h = 1469598103934665603ull;
+    const unsigned char *p = reinterpret_cast<const unsigned char *>(&c);
+    for (size_t k = 0; k < sizeof c; k++) h = (h ^ p[k]) * 1099511628211ull;
+    return h;
+}
+
+// The verbatim sections.  The state blob is carved in one order (carve_state): everything a step reads lies in two runs around the
+// fused step's ready queues (entries of one launch, tagged with its step: nothing to keep) -- env and sender blocks with their
+// shadows, refill rows, restart statistics, class counts, cursors, fctl / any_done, pool stack heights and stacks, history.
+struct SnapLayout {
+    char *ptr[kSnapRings];
+    size_t bytes[kSnapRings];
+    size_t offset[kSnapSections];
+};
+void snap_layout(const pcc_sim_t *sim, SnapLayout &L) {
+    const Dev &d = sim->d;
+    char *a0 = reinterpret_cast<char *>(d.env), *a1 = reinterpret_cast<char *>(d.fctl + (size_t)kListBufs * kXcds * kFctlWords * kCursorStride);
+    char *b0 = reinterpret_cast<char *>(d.any_done), *b1 = reinterpret_cast<char *>(d.hist + (size_t)d.n * d.ns * d.HF);
+    L.ptr[kSnapStateA] = a0; L.bytes[kSnapStateA] = (size_t)(a1 - a0);
+    L.ptr[kSnapStateB] = b0; L.bytes[kSnapStateB] = (size_t)(b1 - b0);
+    L.ptr[kSnapLists] = static_cast<char *>(sim->list_blob); L.bytes[kSnapLists] = sim->list_bytes;
+    size_t off = snap_align(sizeof(SnapHeader));
+    for (int k = 0; k < kSnapRings; k++) { L.offset[k] = off; off = snap_align(off + L.bytes[k]); }
+    L.offset[kSnapRings] = off;
+}
+
+void snap_own_regions(const pcc_sim_t *sim, uint64_t *base, uint64_t *bytes) {
+    for (int c = 0; c < kMaxTiers; c++) { base[c] = reinterpret_cast<uint64_t>(sim->tier_blob[c]); bytes[c] = sim->tier_blob[c] ? sim->tier_bytes[c] : 0; }
+    base[kMaxTiers] = reinterpret_cast<uint64_t>(sim->shadow_blob); bytes[kMaxTiers] = sim->shadow_blob ? sim->shadow_bytes : 0;
+}
+
+// the ring kernels' scratch, allocated at the first use (a tile count per 64 rings, control words, the list of long rings)
+int snap_scratch(pcc_sim_t *sim, SnapScratch &s) {
+    const size_t tile_b = snap_align((size_t)snap_tiles(sim->d) * sizeof(unsigned long long)), ctl_b = 256;
+    const size_t want = tile_b + ctl_b + (size_t)snap_rings(sim->d) * sizeof(ulonglong2);
+    if (!sim->snap_blob) {
+        if (hipMalloc(&sim->snap_blob, want) != hipSuccess) { sim->snap_blob = nullptr; return fail(PCC_ENOMEM, "hipMalloc(%zu) for the snapshot scratch failed", want); }
+        if (hipMemset(sim->snap_blob, 0, want) != hipSuccess) return fail(PCC_EHIP, "hipMemset of the snapshot scratch failed");
+        sim->snap_bytes = want;
+    }
+    char *b = static_cast<char *>(sim->snap_blob);
+    s.tile = reinterpret_cast<unsigned long long *>(b);
+    s.total = reinterpret_cast<unsigned long long *>(b + tile_b);
+    s.ctl = reinterpret_cast<uint32_t *>(b + tile_b + 128);
+    s.longs = reinterpret_cast<ulonglong2 *>(b + tile_b + ctl_b);
+    return PCC_OK;
+}
+
+// what this change does not snapshot, and the states a snapshot cannot be taken in (or restored over)
+int snap_refuse(const pcc_sim_t *sim, const char *call) {
+    if (!sim) return fail(PCC_EINVAL, "%s: sim is NULL", call);
+    if (sim->d.engine)
+        return fail(PCC_EINVAL, "%s: the event-loop build (latency noise; congestion window with two senders) keeps its packets in heaps, which a snapshot does not hold", call);
+    if (sim->fused) return fail(PCC_EINVAL, "%s: a handle with the one-launch step on (PCC_TUNE_FUSED) keeps ready queues, which a snapshot does not hold", call);
+    if (sim->send_pending) return fail(PCC_ESTATE, "%s between pcc_step_send and pcc_step_retire", call);
+    if (!sim->ever_reset || sim->pools_pending) return fail(PCC_ESTATE, "%s needs a full pcc_reset before it (nothing is allocated or started before that)", call);
+    // (two rings per sender block, shadows included: the ring kernels index rings and tiles with room to spare below 2^30)
+    if (snap_rings(sim->d) > ((int64_t)1 << 30)) return fail(PCC_EINVAL, "%s: more than 2^29 sender blocks (shadows included)", call);
+    return PCC_OK;
+}
+
+// Everything the handle still has on its side streams is ordered before what `st` does next: the restarts owed (as pcc_get_state
+// does) and the refills in flight
+int snap_quiesce(pcc_sim_t *sim, hipStream_t st) {
+    const int rc = flush_restarts(sim, st);
+    if (rc != PCC_OK) return rc;
+    for (int k = 0; k < 4; k++)
+        if (sim->refill_recorded[k] && hipStreamWaitEvent(st, sim->ev_refill[k], 0) != hipSuccess) return fail(PCC_EHIP, "hipStreamWaitEvent failed");
+    return PCC_OK;
+}
+
+}  // namespace
+
+int64_t pcc_snapshot_bytes(pcc_sim_t *sim, void *stream) {
+    int rc = snap_refuse(sim, "pcc_snapshot_bytes");
+    if (rc != PCC_OK) return rc;
+    DeviceGuard guard(sim->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SnapScratch s;
+    SnapLayout L;
+    SnapRegions r;
+    if ((rc = snap_scratch(sim, s)) != PCC_OK || (rc = snap_quiesce(sim, st)) != PCC_OK) return rc;
+    snap_layout(sim, L);
+    snap_own_regions(sim, r.src, r.bytes);
+    memcpy(r.dst, r.src, sizeof r.dst);
+    launch_snap_count_scan(sim->d, r, s, nullptr, 0, ~0ull, 0, false, st);
+    unsigned long long records = 0;
+    if (hipGetLastError() != hipSuccess || hipMemcpyAsync(&records, s.total, sizeof records, hipMemcpyDeviceToHost, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess)
+        return fail(PCC_EHIP, "counting the live ring records failed");
+    return (int64_t)(L.offset[kSnapRings] + (size_t)records * sizeof(double2));
+}
+
+int pcc_snapshot(pcc_sim_t *sim, void *buf, int64_t bytes, void *stream) {
+    int rc = snap_refuse(sim, "pcc_snapshot");
+    if (rc != PCC_OK) return rc;
+    if (!buf || (reinterpret_cast<uintptr_t>(buf) & 15u)) return fail(PCC_EINVAL, "pcc_snapshot: buf is NULL or not 16-byte aligned");
+    SnapLayout L;
+    snap_layout(sim, L);
+    if (bytes < (int64_t)L.offset[kSnapRings])
+        return fail(PCC_EINVAL, "pcc_snapshot: bytes=%lld is less than the header and the verbatim sections alone (%zu); pcc_snapshot_bytes says what a snapshot needs",
+                    (long long)bytes, L.offset[kSnapRings]);
+    DeviceGuard guard(sim->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    SnapScratch s;
+    if ((rc = snap_scratch(sim, s)) != PCC_OK || (rc = snap_quiesce(sim, st)) != PCC_OK) return rc;
+    SnapHeader h;
+    memset(&h, 0, sizeof h);
+    h.magic = kSnapMagic; h.version = kSnapVersion; h.header_bytes = (uint32_t)sizeof h;
+    snap_config(sim, h.cfg);
+    h.fingerprint = snap_fingerprint(h.cfg);
+    h.host.host_steps = sim->host_steps; h.host.step_seq = sim->step_seq; h.host.params_gen = sim->d.params_gen;
+    h.host.read_buf = sim->read_buf; h.host.fill_buf = sim->fill_buf; h.host.clean_buf = sim->clean_buf; h.host.shadows = sim->d.shadows;
+    h.host.lockstep = sim->lockstep; h.host.read_has_restarts = sim->read_has_restarts;
+    snap_own_regions(sim, h.region_base, h.region_bytes);
+    for (int k = 0; k < kSnapRings; k++) h.section[k] = SnapSection{L.offset[k], L.bytes[k]};
+    h.section[kSnapRings] = SnapSection{L.offset[kSnapRings], 0};
+    h.truncated = 1u;   // (until the scan has said that the records fit)
+    char *out = static_cast<char *>(buf);
+    launch_snap_header(h, out, st);
+    for (int k = 0; k < kSnapRings; k++)
+        if (hipMemcpyAsync(out + L.offset[k], L.ptr[k], L.bytes[k], hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return fail(PCC_EHIP, "pcc_snapshot: copying section %d failed", k);
+    SnapRegions r;
+    memcpy(r.src, h.region_base, sizeof r.src); memcpy(r.bytes, h.region_bytes, sizeof r.bytes); memcpy(r.dst, r.src, sizeof r.dst);
+    const uint64_t room = ((uint64_t)bytes - L.offset[kSnapRings]) / sizeof(double2);
+    launch_snap_count_scan(sim->d, r, s, reinterpret_cast<SnapHeader *>(out), L.offset[kSnapRings], room, 0, false, st);
+    launch_snap_move(sim->d, r, s, reinterpret_cast<double2 *>(out + L.offset[kSnapRings]), false, st);
+    return check_hip(hipGetLastError(), "snapshot kernel launch");
+}
+
+int pcc_restore(pcc_sim_t *sim, const void *buf, int64_t bytes, void *stream) {
+    int rc = snap_refuse(sim, "pcc_restore");
+    if (rc != PCC_OK) return rc;
+    if (!buf || (reinterpret_cast<uintptr_t>(buf) & 15u)) return fail(PCC_EINVAL, "pcc_restore: buf is NULL or not 16-byte aligned");
+    if (bytes < (int64_t)sizeof(SnapHeader)) return fail(PCC_EINVAL, "pcc_restore: bytes=%lld is less than a snapshot's header (%zu)", (long long)bytes, sizeof(SnapHeader));
+    DeviceGuard guard(sim->device);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    // ---- validation, all of it on the host, before anything is launched or modified
+    SnapHeader h;
+    if (hipMemcpyAsync(&h, buf, sizeof h, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+        return fail(PCC_EHIP, "pcc_restore: reading the header failed");
+    if (h.magic != kSnapMagic) return fail(PCC_EINVAL, "pcc_restore: magic: the buffer does not hold a snapshot");
+    if (h.version != kSnapVersion || h.header_bytes != sizeof h)
+        return fail(PCC_EINVAL, "pcc_restore: version %u (header of %u bytes): this library reads version %u (%zu bytes)", h.version, h.header_bytes, kSnapVersion, sizeof h);
+    SnapConfig own;
+    snap_config(sim, own);
+#define PCC_SNAP_INT(field, name) \
+    if (h.cfg.field != own.field) return fail(PCC_EINVAL, "pcc_restore: %s: the snapshot has %lld, this handle %lld", name, (long long)h.cfg.field, (long long)own.field)
+#define PCC_SNAP_REAL(field, name) \
+    if (!(h.cfg.field == own.field)) return fail(PCC_EINVAL, "pcc_restore: %s: the snapshot has %.17g, this handle %.17g", name, (double)h.cfg.field, (double)own.field)
+    PCC_SNAP_INT(n, "envs");
+    PCC_SNAP_INT(ns, "senders");
+    PCC_SNAP_INT(H, "history length");
+    PCC_SNAP_INT(F, "features");
+    for (int f = 0; f < kMaxFeatures; f++) PCC_SNAP_INT(fid[f], "feature ids");
+    PCC_SNAP_INT(ring_capacity, "ring capacity");
+    PCC_SNAP_INT(n_tiers, "ring tiers");
+    PCC_SNAP_INT(cap0, "tier-0 ring capacity");
+    PCC_SNAP_INT(gid_base, "global env id base");
+    PCC_SNAP_INT(parts, "partitions");
+    for (int c = 1; c < kMaxTiers; c++) PCC_SNAP_INT(tier_slots[c], "ring pool slots (pcc_set_ring_pools)");
+    PCC_SNAP_INT(tier_slots[0], "tier-0 slots");
+    PCC_SNAP_INT(rng_mode, "rng mode");
+    PCC_SNAP_INT(trace_stride, "trace stride");
+    if (h.cfg.key0 != own.key0 || h.cfg.key1 != own.key1)
+        return fail(PCC_EINVAL, "pcc_restore: seed: the snapshot has %llu, this handle %llu", ((unsigned long long)h.cfg.key1 << 32) | h.cfg.key0, ((unsigned long long)own.key1 << 32) | own.key0);
+    PCC_SNAP_INT(link_arrays, "link parameter arrays (pcc_set_link_params: given or not)");
+    for (int k = 0; k < 5; k++) { PCC_SNAP_REAL(lo[k], "parameter ranges"); PCC_SNAP_REAL(hi[k], "parameter ranges"); }
+    PCC_SNAP_INT(use_cwnd, "cwnd mode");
+    PCC_SNAP_REAL(delta_scale, "delta scale");
+    PCC_SNAP_INT(max_steps, "max steps");
+#undef PCC_SNAP_INT
+#undef PCC_SNAP_REAL
+    if (h.fingerprint != snap_fingerprint(own)) return fail(PCC_EINVAL, "pcc_restore: fingerprint: the snapshot's configuration is not this handle's");
+    if (h.truncated) return fail(PCC_EINVAL, "pcc_restore: truncated: the snapshot was taken into a buffer smaller than pcc_snapshot_bytes asked for and holds no ring records");
+    SnapLayout L;
+    snap_layout(sim, L);
+    for (int k = 0; k < kSnapRings; k++)
+        if (h.section[k].offset != L.offset[k] || h.section[k].bytes != L.bytes[k])
+            return fail(PCC_EINVAL, "pcc_restore: section table: section %d is %llu bytes at %llu, this handle's is %zu at %zu", k,
+                        (unsigned long long)h.section[k].bytes, (unsigned long long)h.section[k].offset, L.bytes[k], L.offset[k]);
+    if (h.section[kSnapRings].offset != L.offset[kSnapRings] || h.ring_records > (~0ull - L.offset[kSnapRings]) / sizeof(double2) ||
+        h.total_bytes != L.offset[kSnapRings] + h.ring_records * sizeof(double2))
+        return fail(PCC_EINVAL, "pcc_restore: section table: %llu ring records at %llu do not make the %llu bytes the header states",
+                    (unsigned long long)h.ring_records, (unsigned long long)h.section[kSnapRings].offset, (unsigned long long)h.total_bytes);
+    if ((uint64_t)bytes < h.total_bytes)
+        return fail(PCC_EINVAL, "pcc_restore: bytes=%lld is less than the %llu bytes the header states", (long long)bytes, (unsigned long long)h.total_bytes);
+    if (h.host.read_buf < -1 || h.host.read_buf >= kListBufs || h.host.fill_buf < 0 || h.host.fill_buf >= kListBufs || h.host.clean_buf < -1 ||
+        h.host.clean_buf >= kListBufs)
+        return fail(PCC_EINVAL, "pcc_restore: host fields: list buffers %d / %d / %d out of range", h.host.read_buf, h.host.fill_buf, h.host.clean_buf);
+    SnapRegions r;
+    memcpy(r.src, h.region_base, sizeof r.src); memcpy(r.bytes, h.region_bytes, sizeof r.bytes);
+    uint64_t own_bytes[kSnapRegions];
+    snap_own_regions(sim, r.dst, own_bytes);
+    for (int c = 0; c < kMaxTiers; c++)
+        if (r.bytes[c] != own_bytes[c]) return fail(PCC_EINVAL, "pcc_restore: ring regions: tier %d is %llu bytes in the snapshot, %llu here", c, (unsigned long long)r.bytes[c], (unsigned long long)own_bytes[c]);
+    if (r.bytes[kMaxTiers] != 0 ? r.bytes[kMaxTiers] != shadow_ring_bytes(sim->d) : h.host.shadows != 0)
+        return fail(PCC_EINVAL, "pcc_restore: ring regions: the shadows' rings are %llu bytes in the snapshot, %zu here", (unsigned long long)r.bytes[kMaxTiers], shadow_ring_bytes(sim->d));
+    // (a snapshot taken out of lockstep into a handle that never left it: the shadows' private rings are allocated now, as the
+    // first step out of lockstep would -- the one allocation, and the one device synchronization, a restore can make)
+    if (r.bytes[kMaxTiers] != 0 && !alloc_shadow_rings(sim)) return fail(PCC_ENOMEM, "pcc_restore: hipMalloc(%zu) for the shadows' rings failed", shadow_ring_bytes(sim->d));
+    snap_own_regions(sim, r.dst, own_bytes);
+    SnapScratch s;
+    if ((rc = snap_scratch(sim, s)) != PCC_OK) return rc;
+    // ---- the target's own work on its side streams ends first (refills write shadow blocks); what it was owed is void
+    for (int k = 0; k < 4; k++) {
+        if (sim->refill_recorded[k]) (void)hipStreamWaitEvent(st, sim->ev_refill[k], 0);
+        sim->refill_recorded[k] = false;
+    }
+    const char *in = static_cast<const char *>(buf);
+    for (int k = 0; k < kSnapRings; k++)
+        if (hipMemcpyAsync(L.ptr[k], in + L.offset[k], L.bytes[k], hipMemcpyDeviceToDevice, st) != hipSuccess)
+            return fail(PCC_EHIP, "pcc_restore: copying section %d failed (a full pcc_reset must follow)", k);
+    launch_snap_count_scan(sim->d, r, s, nullptr, 0, h.ring_records, h.ring_records, true, st);
+    launch_snap_move(sim->d, r, s, reinterpret_cast<double2 *>(const_cast<char *>(in) + L.offset[kSnapRings]), true, st);
+    sim->lockstep = h.host.lockstep != 0;
+    sim->host_steps = h.host.host_steps;
+    sim->step_seq = sim->d.step_seq = h.host.step_seq;
+    sim->d.params_gen = h.host.params_gen;
+    sim->read_buf = h.host.read_buf; sim->fill_buf = h.host.fill_buf; sim->clean_buf = h.host.clean_buf;
+    sim->read_has_restarts = h.host.read_has_restarts != 0;
+    sim->restarts_pending = false;   // (a snapshot is taken with nothing owed: snap_quiesce)
+    sim->d.shadows = h.host.shadows;
+    sim->last_stream = st;
+    return check_hip(hipGetLastError(), "restore kernel launch");
+}
+
+}  // extern "C"

@@ -34,6 +34,62 @@ def _ptr(t):
     return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
+class EnvSnapshot(object):
+    """What ``BatchedNetworkEnv.snapshot()`` returns: the library's snapshot -- a uint8 tensor, on the env's device unless moved with
+    ``to()`` -- and the Python-side fields that go with it: the env's step counter, whether it was reset, and the constructor
+    arguments of the env it came from (``restore()`` checks them against the target and says which one differs).  A plain object of
+    tensors, numbers and strings: it goes through ``torch.save`` / ``torch.load`` (registered with torch's safe globals where torch
+    has them) and into ``PPO.state_dict()``."""
+
+    MAGIC, VERSION = b"PCCSNAP1", 1   # (pcc-rl_amd/csrc/pcc_snapshot.h: kSnapMagic, kSnapVersion)
+
+    def __init__(self, data, t, was_reset, config, adapter=None):
+        self.data, self.t, self.was_reset, self.config = data, int(t), bool(was_reset), dict(config)
+        self.adapter = adapter   # SimulatedNetworkEnv's own state (its float64 history and counters: numbers and lists), or None
+
+    def to(self, device):
+        """The same snapshot with its bytes on ``device`` (e.g. "cpu" to keep it, or to write it to a file)."""
+        return EnvSnapshot(self.data.to(device), self.t, self.was_reset, self.config, self.adapter)
+
+    @property
+    def nbytes(self):
+        return int(self.data.numel())
+
+    def header(self):
+        """The header's device-written totals: {"ring_records": live in-flight records stored, "total_bytes": ..., "truncated": ...,
+        "header_bytes": ...} -- the last 24 bytes of SnapHeader (pcc-rl_amd/csrc/pcc_snapshot.h), read only from a buffer whose magic
+        and version are the ones this file knows (a newer layout raises instead of being misread)."""
+        first = self.data[:16].cpu().numpy()
+        version, n = (int(v) for v in first[8:16].view(np.uint32))
+        if first[:8].tobytes() != self.MAGIC or version != self.VERSION or not 40 <= n <= self.data.numel():
+            raise ValueError("not a snapshot of format version %d (magic %r, version %d, header of %d bytes)"
+                             % (self.VERSION, first[:8].tobytes(), version, n))
+        tail = self.data[n - 24:n].cpu().numpy()
+        return {"ring_records": int(tail[:8].view(np.uint64)[0]), "total_bytes": int(tail[8:16].view(np.uint64)[0]),
+                "truncated": bool(tail[16:20].view(np.uint32)[0]), "header_bytes": n}
+
+    def __repr__(self):
+        return "EnvSnapshot(%d bytes on %s, t=%d, %s)" % (self.nbytes, self.data.device, self.t, self.config)
+
+
+if hasattr(torch.serialization, "add_safe_globals"):
+    torch.serialization.add_safe_globals([EnvSnapshot])
+
+
+class GroupedEnvSnapshot(object):
+    """The snapshots of a ``GroupedNetworkEnv``'s groups, in group order."""
+
+    def __init__(self, groups):
+        self.groups = list(groups)
+
+    def to(self, device):
+        return GroupedEnvSnapshot([g.to(device) for g in self.groups])
+
+
+if hasattr(torch.serialization, "add_safe_globals"):
+    torch.serialization.add_safe_globals([GroupedEnvSnapshot])
+
+
 class BatchedNetworkEnv(object):
     """N single-bottleneck congestion-control envs on one MI355X.
 
@@ -84,6 +140,9 @@ class BatchedNetworkEnv(object):
         self.auto_reset, self.record_steps, self.new_tensors = bool(auto_reset), bool(record_steps), bool(new_tensors)
         self.max_steps = int(max_steps)
         self.seed_value = int(seed)
+        self._ring_pools = None if ring_pools is None else tuple(int(v) for v in ring_pools)
+        self._env_gid_base, self._ring_capacity = int(env_gid_base), int(ring_capacity) or DEFAULT_RING_CAPACITY
+        self._delta_scale = float(DELTA_SCALE if delta_scale is None else delta_scale)
 
         L = lib()
         fids = (ctypes.c_int32 * len(self.feature_ids))(*self.feature_ids)
@@ -333,6 +392,57 @@ class BatchedNetworkEnv(object):
                                   1 if self.auto_reset else 0, self._stream()))
         self._t += T
 
+    # ------------------------------------------------------------------ snapshot / restore
+    def _snapshot_config(self):
+        """What a snapshot's source and target must share, as the constructor names it (the library checks the same and more)."""
+        return {"n_envs": self.n_envs, "n_senders": self.n_senders, "history_len": self.history_len, "features": list(self.features),
+                "seed": self.seed_value, "env_gid_base": self._env_gid_base, "ring_capacity": self._ring_capacity,
+                "ring_pools": None if self._ring_pools is None else list(self._ring_pools), "max_steps": self.max_steps,
+                "delta_scale": self._delta_scale, "use_cwnd": self.use_cwnd, "latency_noise": self.latency_noise,
+                "loss_trace": self._trace is not None, "link_params": self._params is not None}
+
+    def snapshot(self):
+        """The env's whole dynamic state as an ``EnvSnapshot`` (pcc_snapshot: the state arrays verbatim, the in-flight rings compacted
+        to their live records).  ``restore()`` of it -- into this env or another one of the same configuration that has been reset
+        once -- makes every later call return what this env returns from here on, bit for bit.  Taking it changes nothing.
+        Synchronizes the env's stream once (to learn the size).  Not with ``latency_noise``, ``use_cwnd`` on two senders or the
+        one-launch step; the env's own output tensors, link-parameter tensors and loss trace are not part of it."""
+        if not self._was_reset:
+            raise PccError(-5, "snapshot() before reset()")
+        n = int(self._L.pcc_snapshot_bytes(self._h, self._stream()))
+        if n < 0:
+            check(n)
+        with torch.cuda.device(self.device):
+            data = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        check(self._L.pcc_snapshot(self._h, _ptr(data), n, self._stream()))
+        return EnvSnapshot(data, self._t, self._was_reset, self._snapshot_config())
+
+    def restore(self, snap):
+        """Put the env into the state ``snap`` holds (pcc_restore).  The env must have the snapshot's configuration and have been
+        reset once; a mismatch raises before anything is touched (ValueError for what the constructor names, PccError from the
+        library's own checks)."""
+        if not isinstance(snap, EnvSnapshot):
+            raise TypeError("restore() takes the EnvSnapshot that snapshot() returned")
+        if not self._was_reset:
+            raise PccError(-5, "restore() before reset(): the target of a restore has been reset once (everything is allocated then)")
+        mine = self._snapshot_config()
+        for key, value in mine.items():
+            if key not in snap.config or snap.config[key] != value:
+                if key == "ring_pools" and (value is None or snap.config.get(key) is None):
+                    raise ValueError("restore: ring_pools: the snapshot's env had %r, this one %r -- the default pool sizes depend on the "
+                                     "free device memory: two envs that exchange snapshots name them (ring_pools=...)"
+                                     % (snap.config.get(key), value))
+                raise ValueError("restore: %s: the snapshot's env had %r, this one %r" % (key, snap.config.get(key), value))
+        data = snap.data
+        if data.dtype != torch.uint8 or data.dim() != 1:
+            raise ValueError("restore: the snapshot's data is not a uint8 vector")
+        if data.device != self.device:
+            data = data.to(self.device)
+        data = data.contiguous()
+        check(self._L.pcc_restore(self._h, _ptr(data), int(data.numel()), self._stream()))
+        data.record_stream(torch.cuda.current_stream(self.device))
+        self._t, self._was_reset = snap.t, True
+
     # ------------------------------------------------------------------ introspection
     def state(self, name):
         """Copy of one internal state field as a tensor (see native.FIELDS)."""
@@ -463,6 +573,24 @@ class GroupedNetworkEnv(object):
         with torch.cuda.stream(self.streams[g]):
             return self.groups[g].step(actions)
 
+    def snapshot(self):
+        """Every group's snapshot, taken on the group's stream (``GroupedEnvSnapshot``); synchronizes."""
+        snaps = []
+        for g in range(self.n_groups):
+            with torch.cuda.stream(self.streams[g]):
+                snaps.append(self.groups[g].snapshot())
+        self.synchronize()
+        return GroupedEnvSnapshot(snaps)
+
+    def restore(self, snap):
+        """Restore every group from its snapshot, on the group's stream; synchronizes."""
+        if not isinstance(snap, GroupedEnvSnapshot) or len(snap.groups) != self.n_groups:
+            raise ValueError("restore: a GroupedEnvSnapshot of %d groups is needed" % self.n_groups)
+        for g in range(self.n_groups):
+            with torch.cuda.stream(self.streams[g]):
+                self.groups[g].restore(snap.groups[g])
+        self.synchronize()
+
     def reset(self):
         """Reset every group; returns the observations [n_envs, ...] (synchronizes)."""
         obs = [self.reset_group(g) for g in range(self.n_groups)]
@@ -572,6 +700,25 @@ class SimulatedNetworkEnv(object):
 
     def render(self, mode="human"):
         pass
+
+    def snapshot(self):
+        """The simulator's state (``BatchedNetworkEnv.snapshot``) with the adapter's own: its float64 history and its counters."""
+        snap = self._env.snapshot()
+        snap.adapter = {"hist": None if self._hist is None else [h.tolist() for h in self._hist], "steps_taken": self.steps_taken,
+                        "reward_sum": self.reward_sum, "reward_ewma": self.reward_ewma, "episodes_run": self.episodes_run,
+                        "run_dur": self.run_dur, "events": [dict(e) for e in self.event_record["Events"]]}
+        return snap
+
+    def restore(self, snap):
+        """Back to the state ``snap`` holds: the simulator's and the adapter's own (``snap`` must come from a SimulatedNetworkEnv)."""
+        a = getattr(snap, "adapter", None)
+        if a is None:
+            raise ValueError("restore: this snapshot holds no SimulatedNetworkEnv state (it was taken from a BatchedNetworkEnv)")
+        self._env.restore(snap)
+        self._hist = None if a["hist"] is None else [np.array(h, dtype=np.float64) for h in a["hist"]]
+        self.steps_taken, self.reward_sum, self.reward_ewma = a["steps_taken"], a["reward_sum"], a["reward_ewma"]
+        self.episodes_run, self.run_dur = a["episodes_run"], a["run_dur"]
+        self.event_record = {"Events": [dict(e) for e in a["events"]]}
 
     def close(self):
         self._env.close()

@@ -43,7 +43,7 @@ TUNE = {
 SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params", "pcc_set_param_ranges",
            "pcc_set_rng", "pcc_set_seed", "pcc_set_tuning", "pcc_set_ring_pools", "pcc_set_cwnd_mode", "pcc_set_latency_noise", "pcc_set_delta_scale", "pcc_set_max_steps", "pcc_reset", "pcc_step", "pcc_step_many", "pcc_rollout", "pcc_step_send",
            "pcc_step_retire",
-           "pcc_get_state", "pcc_restart_stats", "pcc_fused_steps", "pcc_debug_addresses", "pcc_metric_info", "pcc_device_bytes", "pcc_debug_timeline", "pcc_debug_pass_stats",
+           "pcc_get_state", "pcc_snapshot_bytes", "pcc_snapshot", "pcc_restore", "pcc_restart_stats", "pcc_fused_steps", "pcc_debug_addresses", "pcc_metric_info", "pcc_device_bytes", "pcc_debug_timeline", "pcc_debug_pass_stats",
            "pcc_policy_act", "pcc_ppo_supported", "pcc_ppo_scratch_floats", "pcc_ppo_minibatch_step", "pcc_gae"]
 
 
@@ -101,6 +101,12 @@ def lib():
     L.pcc_step_send.argtypes = [vp, vp, i32, vp]
     L.pcc_step_retire.argtypes = [vp, vp, vp, vp, vp, i32, vp]
     L.pcc_get_state.argtypes = [vp, i32, vp, vp]
+    L.pcc_snapshot_bytes.restype = i64
+    L.pcc_snapshot_bytes.argtypes = [vp, vp]
+    L.pcc_snapshot.restype = i32
+    L.pcc_snapshot.argtypes = [vp, vp, i64, vp]
+    L.pcc_restore.restype = i32
+    L.pcc_restore.argtypes = [vp, vp, i64, vp]
     L.pcc_restart_stats.restype = i32
     L.pcc_restart_stats.argtypes = [vp, vp, vp]
     L.pcc_fused_steps.restype = i32

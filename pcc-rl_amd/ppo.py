@@ -384,6 +384,49 @@ class PPO(object):
         ent = float(self.policy.log_std.detach().sum()) + 0.5 * (1.0 + math.log(2.0 * math.pi)) * self.policy.log_std.numel()
         return {"pg": -st[0], "vf": 0.5 * st[1], "entropy": ent, "clip_frac": st[2]}
 
+    def state_dict(self):
+        """Everything the next iterate() depends on, for a checkpoint that resumes bit for bit: the parameters and Adam's state (the
+        flat block with m, v, t on the fused path, the module's and the torch optimiser's state_dict on the framework path), the
+        observation the next rollout starts from, torch's CPU and device generator states (the rollout's noise and the
+        minibatch permutations come from the device's), and the env's snapshot (BatchedNetworkEnv.snapshot: not with the env options it
+        refuses).  torch.save() takes it as it is."""
+        dev = torch.device(self.env.device)
+        sd = {"format": 1, "fused_update": self.fused_update, "obs_dim": int(self.env.obs_dim), "n_envs": int(self.env.n_envs),
+              "obs": self.obs.detach().clone(), "torch_rng": torch.get_rng_state(),
+              "device_rng": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None, "env": self.env.snapshot()}
+        if self.fused_update:
+            sd.update(flat=self.flat.detach().clone(), adam_m=self.adam_m.clone(), adam_v=self.adam_v.clone(), adam_t=int(self.adam_t))
+        else:
+            sd.update(policy={k: v.detach().clone() for k, v in self.policy.state_dict().items()}, opt=self.opt.state_dict())
+        return sd
+
+    def load_state_dict(self, sd):
+        """Continue from a state_dict() of a PPO of the same construction (env configuration, arch, update path): the env is restored
+        from its snapshot (it must have been reset once: the constructor did that), then the parameters, the optimiser, the
+        observation and the generator states."""
+        dev = torch.device(self.env.device)
+        if sd.get("format") != 1:
+            raise ValueError("not a PPO.state_dict() of this version")
+        if bool(sd["fused_update"]) != self.fused_update or sd["obs_dim"] != int(self.env.obs_dim) or sd["n_envs"] != int(self.env.n_envs):
+            raise ValueError("the checkpoint is of another PPO: fused_update=%s, obs_dim=%d, n_envs=%d; this one: %s, %d, %d"
+                             % (sd["fused_update"], sd["obs_dim"], sd["n_envs"], self.fused_update, self.env.obs_dim, self.env.n_envs))
+        if self.fused_update and sd["flat"].numel() != self.flat.numel():
+            raise ValueError("the checkpoint's policy has %d parameters, this one %d (another --arch)" % (sd["flat"].numel(), self.flat.numel()))
+        self.env.restore(sd["env"])
+        if self.fused_update:
+            with torch.no_grad():
+                self.flat.copy_(sd["flat"])   # (the module's parameters are views of it: share_flat)
+                self.adam_m.copy_(sd["adam_m"])
+                self.adam_v.copy_(sd["adam_v"])
+            self.adam_t = int(sd["adam_t"])
+        else:
+            self.policy.load_state_dict(sd["policy"])
+            self.opt.load_state_dict(sd["opt"])
+        self.obs = sd["obs"].to(dev).clone()
+        torch.set_rng_state(sd["torch_rng"].cpu())
+        if dev.type == "cuda" and sd.get("device_rng") is not None:
+            torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)
+
     def iterate(self):
         obs_b, act_b, logp_b, adv, ret, rew = self.collect()
         stats = self.update(obs_b, act_b, logp_b, adv, ret)

@@ -1,0 +1,80 @@
+#!/usr/bin/env python3
+"""Train a population of PCC rate controllers -- K independent PPO learners on K slices of one env batch (pcc-rl_amd/ppo.py:
+PopulationPPO): seeds for a learning curve, or a sweep over learning rates, entropy coefficients and discount factors.
+
+    python examples/train_population.py --members 8 --envs 65536 --iters 50                  # eight seeds
+    python examples/train_population.py --members 4 --envs 32768 --lrs 1e-3,3e-4,1e-4,3e-5   # a learning-rate sweep
+    python examples/train_population.py --members 4 --envs 32768 --checkpoint pop.pt         # ... interrupted ... (--ring-pools 1,2,8 at 65 536 envs)
+    python examples/train_population.py --members 4 --envs 32768 --resume pop.pt --checkpoint pop.pt
+
+One line per iteration with every member's episode return.  --lrs / --ent-coefs / --gammas take one value or one per member."""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import pcc_rl_amd  # noqa: E402
+from pcc_rl_amd.ppo import PopulationPPO  # noqa: E402
+
+
+def values(text, default):
+    """one value for all members, or one per member (PopulationPPO checks the count)"""
+    if not text:
+        return default
+    v = [float(x) for x in text.split(",")]
+    return v[0] if len(v) == 1 else v
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--members", type=int, default=8)
+    ap.add_argument("--envs", type=int, default=65536, help="of the whole batch: every member trains on envs / members of them")
+    ap.add_argument("--iters", type=int, default=50)
+    ap.add_argument("--horizon", type=int, default=64)
+    ap.add_argument("--arch", default="32,16")
+    ap.add_argument("--lrs", default="")
+    ap.add_argument("--ent-coefs", default="")
+    ap.add_argument("--gammas", default="")
+    ap.add_argument("--seeds", default="", help="one per member (default 0, 1, ...)")
+    ap.add_argument("--save", default="", help="write every member's policy state_dict here (a list) at the end")
+    ap.add_argument("--checkpoint", default="", help="write the whole training state here every --checkpoint-every iterations and at the end")
+    ap.add_argument("--checkpoint-every", type=int, default=10)
+    ap.add_argument("--resume", default="", help="continue from a --checkpoint file of a run with the same --members, --envs, --horizon and --arch")
+    ap.add_argument("--ring-pools", default="", help="div1,div2,div3 of BatchedNetworkEnv(ring_pools=...); with --checkpoint / --resume the "
+                    "default is 2,8,32 (the library's own default depends on the free device memory, and a snapshot needs equal pools): "
+                    "untrained policies ran those dry at 65 536 envs (PCC_FLAG_POOL_EXHAUSTED) -- 1,2,8 held there; the same on the run that resumes")
+    args = ap.parse_args()
+    pools = tuple(int(x) for x in args.ring_pools.split(",")) if args.ring_pools else ((2, 8, 32) if args.checkpoint or args.resume else None)
+    env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0, ring_pools=pools)
+    pop = PopulationPPO(env, args.members, arch=tuple(int(x) for x in args.arch.split(",")), horizon=args.horizon,
+                        lr=values(args.lrs, 1e-3), ent_coef=values(args.ent_coefs, 0.01),
+                        gamma=values(args.gammas, 0.99),
+                        seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None)
+    first = 0
+    if args.resume:
+        ck = torch.load(args.resume)
+        pop.load_state_dict(ck["population"])
+        first = int(ck["iters_done"])
+        print("resumed %s after %d iterations" % (args.resume, first))
+
+    def checkpoint(done):
+        torch.save({"population": pop.state_dict(), "iters_done": done}, args.checkpoint + ".tmp")
+        os.replace(args.checkpoint + ".tmp", args.checkpoint)
+
+    t0 = time.perf_counter()
+    for it in range(first, args.iters):
+        s = pop.iterate()
+        if args.checkpoint and ((it + 1) % max(args.checkpoint_every, 1) == 0 or it + 1 == args.iters):
+            checkpoint(it + 1)
+        steps = (it + 1 - first) * args.envs * args.horizon
+        print("iter %3d  env-steps %11d  %.0f env-steps/s incl. learning  return per member: %s"
+              % (it, steps, steps / (time.perf_counter() - t0), " ".join("%7.1f" % (r * env.max_steps) for r in s["mean_step_reward"])))
+    if args.save:
+        torch.save([p.state_dict() for p in pop.policies], args.save)
+
+
+if __name__ == "__main__":
+    main()

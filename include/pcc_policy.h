@@ -67,6 +67,43 @@ int pcc_ppo_minibatch_step(const float *obs, const float *act, const float *logp
 int pcc_gae(const float *rewards, const float *values, const uint8_t *dones, const float *last_value, int T, int64_t n_envs,
             float gamma, float lam, float *adv_out, float *ret_out, void *stream);
 
+/*
+ * A population: n_members independent policies on n_members equal slices of one env batch.  Member m owns the envs (the
+ * columns of [T][n_envs] rows) [m * n_envs / n_members, (m + 1) * n_envs / n_members); n_envs % n_members != 0 returns -1;
+ * 1 <= n_members <= 1024.  Parameter blocks (params, adam_m, adam_v, grad_out) are [n_members][param_stride] floats: each row
+ * has the layout `params` has above in its first n_params floats; param_stride >= n_params and a multiple of 64 floats (every
+ * member's block 256-byte aligned), anything else returns -1; the padding is never read or written.
+ * hyper     caller-owned device floats [n_members][8]: {lr, clip, ent_coef, gamma, lam, 0, 0, 0}
+ *
+ * pcc_policy_act_pop: pcc_policy_act for every member in ONE launch (the member is a grid dimension).  Every output is
+ * bit-identical to n_members calls of pcc_policy_act on the members' row slices with params + m * param_stride: a member's
+ * slice is cut into workgroups and tiles exactly as a stand-alone launch over its rows (no divisibility is asked of the member
+ * size), and in the --arch 32,16 kernel a member's weights stay wave-uniform scalar loads.  The domain and the return codes of
+ * pcc_policy_act.
+ *
+ * pcc_ppo_minibatch_step_pop: pcc_ppo_minibatch_step for every member in TWO launches (gradient, Adam; the member is a grid
+ * dimension).  perm is required: member m takes the samples perm[m * perm_stride + start .. + count), indices into the SAME
+ * flattened [T * N] rollout arrays for every member.  Each member's grid and order of partial sums are those of a stand-alone
+ * call with the same count, so params, adam_m, adam_v, grad_out ([n_members][param_stride], or NULL) and stats_out
+ * ([n_members][4], or NULL) are bit-identical to n_members calls of pcc_ppo_minibatch_step with perm + m * perm_stride and
+ * that member's lr, clip and ent_coef.  A member with lr == 0 in hyper is gradient-only, as there.  scratch is n_members x
+ * pcc_ppo_scratch_floats(obs_dim, h1, h2) floats.  adam_step >= 1 and adam_m / adam_v non-NULL always: the host cannot see
+ * the learning rates.  Returns as pcc_ppo_minibatch_step.
+ *
+ * pcc_gae_pop: pcc_gae with gamma and lambda read per member from hyper; bit-identical to pcc_gae on a contiguous copy of a
+ * member's columns.
+ */
+int pcc_policy_act_pop(const float *obs, int64_t n_envs, int obs_dim, const float *params, int64_t param_stride,
+                       int n_members, int h1, int h2, const float *noise, float *mean_out, float *act_out,
+                       float *logp_out, float *value_out, void *stream);
+int pcc_ppo_minibatch_step_pop(const float *obs, const float *act, const float *logp_old, const float *adv, const float *ret,
+                       const int64_t *perm, int64_t perm_stride, int64_t start, int64_t count, int obs_dim, int h1, int h2,
+                       float *params, float *adam_m, float *adam_v, int64_t param_stride, int n_members, const float *hyper,
+                       int adam_step, float beta1, float beta2, float eps, float *scratch, float *grad_out, float *stats_out,
+                       void *stream);
+int pcc_gae_pop(const float *rewards, const float *values, const uint8_t *dones, const float *last_value, int T,
+                int64_t n_envs, int n_members, const float *hyper, float *adv_out, float *ret_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -91,11 +91,16 @@ class MlpPolicy(nn.Module):
             return [p.detach().reshape(-1) for m in seq if isinstance(m, nn.Linear) for p in (m.weight, m.bias)]
         return torch.cat(net(self.pi) + [self.log_std.detach().reshape(-1)] + net(self.vf)).float().contiguous()
 
-    def share_flat(self):
+    def share_flat(self, into=None):
         """Move every parameter into ONE flat fp32 tensor in flat_params() order -- the module's parameters become views of
         it -- and return it: the fused optimiser step (pcc_ppo_minibatch_step) then updates the weights the framework
-        path and pcc_policy_act read, with no copy in either direction."""
+        path and pcc_policy_act read, with no copy in either direction.  `into`: the flat tensor to move them into (a row
+        of a population's block, PopulationPPO), instead of a new one."""
         flat = self.flat_params().clone()
+        if into is not None:
+            with torch.no_grad():
+                into.copy_(flat)
+            flat = into
         off = 0
 
         def net(seq):
@@ -432,3 +437,220 @@ class PPO(object):
         stats = self.update(obs_b, act_b, logp_b, adv, ret)
         stats["mean_step_reward"] = float(rew.mean())
         return stats
+
+
+# ------------------------------------------------------------------------------------------------------------ population
+def population_sample_index(member, t, env, n_envs, n_members):
+    """The index of member `member`'s sample (step t, its env `env`) in the flattened [T * n_envs] rollout arrays every member
+    shares: member m owns the envs m * n_envs / n_members ... of each row (include/pcc_policy.h).  Integers or tensors."""
+    n_m = n_envs // n_members
+    return t * n_envs + member * n_m + env
+
+
+def population_permutations(T, n_envs, n_members, device="cpu", generator=None):
+    """[n_members][T * n_m] int64: row m is a random permutation of member m's own T * n_m samples, as indices into the shared
+    [T * n_envs] arrays (population_sample_index) -- what pcc_ppo_minibatch_step_pop takes as `perm`.  One draw for all members."""
+    n_m = n_envs // n_members
+    local = torch.rand((n_members, T * n_m), device=device, generator=generator).argsort(dim=1)   # row m: a permutation of 0 .. T n_m - 1
+    member = torch.arange(n_members, device=device).unsqueeze(1)
+    return population_sample_index(member, local // n_m, local % n_m, n_envs, n_members).contiguous()
+
+
+def normalise_per_member(adv, n_members):
+    """PPO.update's advantage normalisation, (a - mean) / (std + 1e-8), for each member over its own samples: the columns
+    m * n_m ... of the [T][N] rows.  Member by member, so that no member's numbers depend on another's."""
+    T, N = adv.shape
+    n_m = N // n_members
+    out = torch.empty_like(adv)
+    for m in range(n_members):
+        a = adv[:, m * n_m:(m + 1) * n_m].contiguous()   # (the sums' order does not depend on where the member's columns sit)
+        out[:, m * n_m:(m + 1) * n_m] = (a - a.mean()) / (a.std() + 1e-8)
+    return out
+
+
+HYPER_COLS = 8   # a row of `hyper` (include/pcc_policy.h): {lr, clip, ent_coef, gamma, lam, 0, 0, 0}
+
+
+class PopulationPPO(object):
+    """`members` independent PPO learners -- each its own policy, Adam state and hyper-parameters -- on `members` equal slices
+    of ONE BatchedNetworkEnv: the env is stepped once per step for the whole batch, and the policy forward, the advantage
+    estimation and the optimiser step are each one library call for all members (include/pcc_policy.h: pcc_policy_act_pop,
+    pcc_gae_pop, pcc_ppo_minibatch_step_pop), bit-identical to the members run one by one through the single-policy entry
+    points.  Seeds for a learning curve, or a sweep over lr / clip / ent_coef / gamma / lam: each is a scalar or one value per
+    member.  Member m's policy starts as PPO(seed=seeds[m])'s: like PPO, construction reseeds torch's global generators
+    (torch.manual_seed, member by member), so they are left seeded by seeds[-1], and the rollout's noise and the minibatch
+    permutations are drawn from the device's from there.  There is no framework path: anything the library has no kernel
+    for raises ValueError."""
+
+    def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
+                 epochs=4, minibatch=None, horizon=64):
+        from .env import BatchedNetworkEnv
+        from .native import lib
+        members = int(members)
+        if members < 1 or members > 1024:
+            raise ValueError("PopulationPPO: members = %d (1 .. 1024)" % members)
+        if len(arch) != 2:
+            raise ValueError("PopulationPPO needs a policy of two hidden layers (arch = %r)" % (tuple(arch),))
+        if int(env.n_envs) % members != 0:
+            raise ValueError("PopulationPPO: %d envs do not divide into %d members" % (env.n_envs, members))
+        cols = []
+        for name, v in (("lr", lr), ("clip", clip), ("ent_coef", ent_coef), ("gamma", gamma), ("lam", lam)):
+            try:
+                vals = [float(v)] * members          # a scalar: a number, a numpy scalar, a 0-dim tensor
+            except (TypeError, ValueError):
+                vals = [float(x) for x in v]
+            if len(vals) != members:
+                raise ValueError("PopulationPPO: %s has %d values for %d members" % (name, len(vals), members))
+            cols.append(vals)
+        seeds = list(range(members)) if seeds is None else [int(x) for x in seeds]
+        if len(seeds) != members:
+            raise ValueError("PopulationPPO: seeds has %d values for %d members" % (len(seeds), members))
+        if not isinstance(env, BatchedNetworkEnv) or torch.device(env.device).type != "cuda" or env.n_senders != 1:
+            raise ValueError("PopulationPPO needs a BatchedNetworkEnv with one sender on the GPU (no GroupedNetworkEnv)")
+        if lib().pcc_ppo_supported(int(env.obs_dim), int(arch[0]), int(arch[1])) != 1:
+            raise ValueError("PopulationPPO: the library has no kernels for %d observations x hidden %s (pcc_ppo_supported)"
+                             % (env.obs_dim, list(arch)))
+        self.env, self.members, self.arch = env, members, (int(arch[0]), int(arch[1]))
+        self.epochs, self.horizon, self.adam_eps = epochs, horizon, 1e-5
+        self.n_member = int(env.n_envs) // members
+        dev = env.device
+        self.hyper_rows = [list(r) + [0.0] * (HYPER_COLS - 5) for r in zip(*cols)]
+        self.hyper = torch.tensor(self.hyper_rows, dtype=torch.float32, device=dev)
+        D = int(env.obs_dim)
+        self.n_params = 2 * (self.arch[0] * D + self.arch[0] + self.arch[1] * self.arch[0] + 2 * self.arch[1] + 1) + 1
+        self.param_stride = (self.n_params + 63) // 64 * 64   # every member's block 256-byte aligned
+        self.flat = torch.zeros((members, self.param_stride), device=dev)
+        self.policies = []
+        for m in range(members):
+            torch.manual_seed(seeds[m])                         # as PPO(seed=seeds[m]) makes its policy
+            pol = MlpPolicy(D, 1, self.arch).to(dev)
+            pol.share_flat(into=self.flat[m, :self.n_params])
+            self.policies.append(pol)
+        self.adam_m, self.adam_v, self.adam_t = torch.zeros_like(self.flat), torch.zeros_like(self.flat), 0
+        self.scratch_floats = lib().pcc_ppo_scratch_floats(D, *self.arch)
+        self.scratch = torch.empty(members * self.scratch_floats, device=dev)
+        self.stats_buf = torch.zeros((members, 4), device=dev)
+        self.obs = env.reset().clone()
+        per_member = self.n_member * horizon
+        self.minibatch = min(per_member, max(2048, per_member // 4)) if minibatch is None else int(minibatch)
+
+    def _stream(self):
+        return ctypes.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+
+    def _act(self, obs, noise, act, logp, val):
+        """The policies on one [N, D] observation row: member m on its slice with its parameters, one launch."""
+        from .native import lib
+        N, D = obs.shape
+        rc = lib().pcc_policy_act_pop(_ptr(obs), N, D, _ptr(self.flat), self.param_stride, self.members, self.arch[0], self.arch[1],
+                                      _ptr(noise), None, _ptr(act), _ptr(logp), _ptr(val), self._stream())
+        if rc != 0:
+            raise RuntimeError("pcc_policy_act_pop failed (%d)" % rc)
+
+    def _gae(self, rew_b, val_b, done_b, last_v):
+        from .native import lib
+        T, N = rew_b.shape
+        adv, ret = torch.empty_like(rew_b), torch.empty_like(rew_b)
+        d8 = done_b.view(torch.uint8)
+        rc = lib().pcc_gae_pop(_ptr(rew_b), _ptr(val_b), _ptr(d8), _ptr(last_v), T, N, self.members, _ptr(self.hyper), _ptr(adv), _ptr(ret),
+                               self._stream())
+        if rc != 0:
+            raise RuntimeError("pcc_gae_pop failed (%d)" % rc)
+        return adv, ret
+
+    def collect(self, noise=None):
+        """One rollout of `horizon` steps of the whole batch: per step pcc_policy_act_pop (every member on its slice) and ONE
+        env step; then the last values, the env's flags, and pcc_gae_pop with every member's gamma and lambda.  noise: the
+        [horizon, n_envs] standard-normal draws (default: drawn here).  Returns PPO.collect()'s tuple; the value and done rows
+        stay in self.val_b / self.done_b."""
+        env, T, N = self.env, self.horizon, int(self.env.n_envs)
+        dev = env.device
+        obs_b = torch.empty((T + 1, N, env.obs_dim), device=dev)
+        act_b = torch.empty((T, N, 1), device=dev)
+        logp_b, val_b, rew_b = (torch.empty((T, N), device=dev) for _ in range(3))
+        done_b = torch.empty((T, N), dtype=torch.bool, device=dev)
+        obs_b[0] = self.obs
+        if noise is None:
+            noise = torch.randn((T, N), device=dev)
+        for t in range(T):
+            self._act(obs_b[t], noise[t], act_b[t].reshape(N), logp_b[t], val_b[t])
+            env.step_into(act_b[t], obs_b[t + 1], rew_b[t], done_b[t])
+        self.obs = obs_b[T].clone()
+        last_v = torch.empty(N, device=dev)
+        self._act(obs_b[T], None, None, None, last_v)
+        env.check_flags()
+        adv, ret = self._gae(rew_b, val_b, done_b, last_v)
+        self.val_b, self.done_b = val_b, done_b
+        return obs_b[:T], act_b, logp_b, adv, ret, rew_b
+
+    def normalise(self, adv):
+        return normalise_per_member(adv, self.members)
+
+    def minibatch_step(self, obs_f, act_f, logp_f, adv_f, ret_f, perm, start, count, grad_out=None):
+        """One optimiser step of every member on its samples perm[m][start : start + count] (global indices into the flattened
+        rollout): two launches (pcc_ppo_minibatch_step_pop)."""
+        from .native import lib
+        if start < 0 or count < 1 or start + count > perm.shape[1]:
+            raise ValueError("minibatch [%d, %d) outside a member's rollout" % (start, start + count))
+        self.adam_t += 1
+        D = obs_f.shape[1]
+        rc = lib().pcc_ppo_minibatch_step_pop(_ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), perm.stride(0),
+                                              start, count, D, self.arch[0], self.arch[1], _ptr(self.flat), _ptr(self.adam_m),
+                                              _ptr(self.adam_v), self.param_stride, self.members, _ptr(self.hyper), self.adam_t, 0.9, 0.999,
+                                              self.adam_eps, _ptr(self.scratch), _ptr(grad_out), _ptr(self.stats_buf), self._stream())
+        if rc != 0:
+            raise RuntimeError("pcc_ppo_minibatch_step_pop failed (%d)" % rc)
+
+    def update(self, obs_b, act_b, logp_b, adv, ret, perms=None):
+        """`epochs` passes over every member's own samples in minibatches of self.minibatch samples per member.  perms: one
+        [members][T * n_m] tensor per epoch (population_permutations; default: drawn here, one draw per epoch)."""
+        T, N = adv.shape
+        n = T * N
+        adv_f = self.normalise(adv).reshape(n)
+        obs_f, act_f = obs_b.reshape(n, -1).contiguous(), act_b.reshape(n).contiguous()
+        logp_f, ret_f = logp_b.reshape(n).contiguous(), ret.reshape(n).contiguous()
+        per_member = T * self.n_member
+        for e in range(self.epochs):
+            perm = perms[e] if perms is not None else population_permutations(T, N, self.members, device=adv.device)
+            for i in range(0, per_member, self.minibatch):
+                self.minibatch_step(obs_f, act_f, logp_f, adv_f, ret_f, perm, i, min(self.minibatch, per_member - i))
+        st = self.stats_buf.tolist()   # of every member's last minibatch
+        log_std = [float(x) for x in self.flat[:, (self.n_params - 1) // 2].tolist()]
+        ent = [x + 0.5 * (1.0 + math.log(2.0 * math.pi)) for x in log_std]
+        return {"pg": [-r[0] for r in st], "vf": [0.5 * r[1] for r in st], "entropy": ent, "clip_frac": [r[2] for r in st]}
+
+    def iterate(self):
+        """collect() + update(); per-member lists of mean_step_reward, pg, vf, entropy, clip_frac."""
+        obs_b, act_b, logp_b, adv, ret, rew = self.collect()
+        stats = self.update(obs_b, act_b, logp_b, adv, ret)
+        stats["mean_step_reward"] = rew.reshape(rew.shape[0], self.members, self.n_member).mean(dim=(0, 2)).tolist()
+        return stats
+
+    def state_dict(self):
+        """Everything the next iterate() depends on (PPO.state_dict's contract): the flat block, Adam's state and step, hyper, the
+        observation, the generator states and the env's snapshot."""
+        dev = torch.device(self.env.device)
+        return {"format": "population-1", "members": self.members, "obs_dim": int(self.env.obs_dim), "n_envs": int(self.env.n_envs),
+                "arch": self.arch, "flat": self.flat.detach().clone(), "adam_m": self.adam_m.clone(), "adam_v": self.adam_v.clone(),
+                "adam_t": int(self.adam_t), "hyper": self.hyper.clone(), "obs": self.obs.detach().clone(),
+                "torch_rng": torch.get_rng_state(), "device_rng": torch.cuda.get_rng_state(dev), "env": self.env.snapshot()}
+
+    def load_state_dict(self, sd):
+        """Continue from a state_dict() of a PopulationPPO of the same construction (env configuration, members, arch)."""
+        dev = torch.device(self.env.device)
+        if sd.get("format") != "population-1":
+            raise ValueError("not a PopulationPPO.state_dict() of this version")
+        mine = (self.members, int(self.env.obs_dim), int(self.env.n_envs), tuple(self.arch))
+        theirs = (sd["members"], sd["obs_dim"], sd["n_envs"], tuple(sd["arch"]))
+        if mine != theirs:
+            raise ValueError("the checkpoint is of another population: (members, obs_dim, n_envs, arch) = %s; this one: %s" % (theirs, mine))
+        self.env.restore(sd["env"])
+        with torch.no_grad():
+            self.flat.copy_(sd["flat"])       # (the policies' parameters are views of its rows)
+            self.adam_m.copy_(sd["adam_m"])
+            self.adam_v.copy_(sd["adam_v"])
+            self.hyper.copy_(sd["hyper"])
+        self.hyper_rows = [[float(x) for x in r] for r in self.hyper.tolist()]
+        self.adam_t = int(sd["adam_t"])
+        self.obs = sd["obs"].to(dev).clone()
+        torch.set_rng_state(sd["torch_rng"].cpu())
+        torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)

@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Device assembly of two source trees of this project, side by side: every unit of build.UNITS compiled with
 build.HIPCC_FLAGS (+ extra flags) --cuda-device-only -S, the per-file __hip_cuid_* lines dropped, split at the kernel
-symbols; per kernel "same" or the number of differing lines, plus the two resource rows where they differ.
+symbols; per kernel "same" or the number of differing lines, plus the two resource rows where they differ.  The compiler numbers
+its local labels by the function's position in the unit (.LBB3_7, .Lfunc_end3, "Header=BB3_4"): that index is blanked, and the
+.section / .globl lines that open a function count with it, not with the one before -- a function added to a unit does not
+make its neighbours differ.
    python tools/asm_diff.py [--units pcc_small,pcc_retire] [--keep DIR] [--jobs N] TREE_A TREE_B [-- -DPCC_PROFILE=1 ...]
 The first line of the report names the two trees as given and the flags."""
 import argparse, difflib, importlib.util, os, re, subprocess, sys, tempfile
@@ -34,17 +37,26 @@ def compile_unit(build, unit, extra, out):
     p = subprocess.run(cmd, stderr=subprocess.PIPE, universal_newlines=True)
     if p.returncode != 0:
         raise RuntimeError("%s failed:\n%s" % (" ".join(cmd), p.stderr[-4000:]))
-    chunks, cur = {"": []}, ""
+    chunks, cur, opening = {"": []}, "", []
     with open(out) as f:
         for line in f:
             if "__hip_cuid" in line:
                 continue
+            line = re.sub(r"(BB|\.Lfunc_begin|\.Lfunc_end|\.Ltmp)\d+", r"\1#", line)
+            if re.match(r"\s*\.(section\s+\.text|globl|protected|weak|hidden|p2align)\b", line):
+                opening.append(line)   # (of the function whose .type line follows)
+                continue
             m = re.match(r"\s*\.type\s+(\S+),@function", line)
             if m:
                 cur = m.group(1)
-                chunks[cur] = []
-            elif line.startswith("\t.amdgpu_metadata") or re.match(r"\s*\.type\s+\S+,@object", line):
-                cur = ""   # (descriptors and metadata: symbol names, kernarg layouts, register counts)
+                chunks[cur] = opening
+                opening = []
+            else:
+                if line.startswith("\t.amdgpu_metadata") or line.startswith("\t.section\t.AMDGPU.gpr_maximums") or re.match(r"\s*\.type\s+\S+,@object", line):
+                    cur = ""   # (descriptors and metadata: symbol names, kernarg layouts, register counts)
+                if opening:    # (they opened no function: they stay with what they stand in -- an object's go outside with it)
+                    chunks[cur] += opening
+                    opening = []
             chunks[cur].append(line)
     return chunks, resource_rows(p.stderr)
 

@@ -6,8 +6,12 @@ PopulationPPO): seeds for a learning curve, or a sweep over learning rates, entr
     python examples/train_population.py --members 4 --envs 32768 --lrs 1e-3,3e-4,1e-4,3e-5   # a learning-rate sweep
     python examples/train_population.py --members 4 --envs 32768 --checkpoint pop.pt         # ... interrupted ... (--ring-pools 1,2,8 at 65 536 envs)
     python examples/train_population.py --members 4 --envs 32768 --resume pop.pt --checkpoint pop.pt
+    python examples/train_population.py --members 8 --lrs 1e-2,3e-3,1e-3,3e-4,1e-4,3e-5,1e-5,3e-6 --pbt-every 5   # population-based training
 
-One line per iteration with every member's episode return.  --lrs / --ent-coefs / --gammas take one value or one per member."""
+One line per iteration with every member's episode return.  --lrs / --ent-coefs / --gammas take one value or one per member.
+--pbt-every N: every N iterations the worst --pbt-frac of the members take over a good member's weights, Adam state and
+hyper-parameters, lr and ent_coef perturbed (PopulationPPO.evolve: one launch, scored by the mean reward over those N iterations);
+the line then also shows every member's parent, lr and ent_coef.  The generation travels in --checkpoint / --resume."""
 import argparse
 import os
 import sys
@@ -43,6 +47,10 @@ def main():
     ap.add_argument("--checkpoint", default="", help="write the whole training state here every --checkpoint-every iterations and at the end")
     ap.add_argument("--checkpoint-every", type=int, default=10)
     ap.add_argument("--resume", default="", help="continue from a --checkpoint file of a run with the same --members, --envs, --horizon and --arch")
+    ap.add_argument("--pbt-every", type=int, default=0, help="evolve the population every N iterations (0: never, a static sweep)")
+    ap.add_argument("--pbt-frac", type=float, default=0.25, help="the share of the members replaced per generation (at most 0.5)")
+    ap.add_argument("--pbt-seed", type=int, default=0)
+    ap.add_argument("--curve", default="", help="write every iteration's returns per member -- and each generation's parents and hyper rows -- here as JSON")
     ap.add_argument("--ring-pools", default="", help="div1,div2,div3 of BatchedNetworkEnv(ring_pools=...); with --checkpoint / --resume the "
                     "default is 2,8,32 (the library's own default depends on the free device memory, and a snapshot needs equal pools): "
                     "untrained policies ran those dry at 65 536 envs (PCC_FLAG_POOL_EXHAUSTED) -- 1,2,8 held there; the same on the run that resumes")
@@ -60,18 +68,38 @@ def main():
         first = int(ck["iters_done"])
         print("resumed %s after %d iterations" % (args.resume, first))
 
+    window = []   # the members' mean step rewards of the iterations since the last generation
+    if args.resume and args.pbt_every > 0:
+        window = [list(r) for r in ck.get("pbt_window", [])]
+
     def checkpoint(done):
-        torch.save({"population": pop.state_dict(), "iters_done": done}, args.checkpoint + ".tmp")
+        torch.save({"population": pop.state_dict(), "iters_done": done, "pbt_window": window}, args.checkpoint + ".tmp")
         os.replace(args.checkpoint + ".tmp", args.checkpoint)
 
+    curve = {"args": vars(args), "returns": [], "generations": []}
     t0 = time.perf_counter()
     for it in range(first, args.iters):
         s = pop.iterate()
+        curve["returns"].append([r * env.max_steps for r in s["mean_step_reward"]])
+        pbt = ""
+        if args.pbt_every > 0:
+            window.append(s["mean_step_reward"])
+            if len(window) >= args.pbt_every:
+                parent, _ = pop.evolve(torch.tensor(window, dtype=torch.float64).mean(dim=0), frac=args.pbt_frac, seed=args.pbt_seed)
+                window = []
+                curve["generations"].append({"after_iter": it, "parents": parent.tolist(), "hyper": pop.hypers()})
+                pbt = "  parents: %s  lr: %s  ent_coef: %s" % (" ".join("%d" % p for p in parent.tolist()),
+                                                             " ".join("%.2e" % h[0] for h in pop.hypers()), " ".join("%.2e" % h[2] for h in pop.hypers()))
         if args.checkpoint and ((it + 1) % max(args.checkpoint_every, 1) == 0 or it + 1 == args.iters):
             checkpoint(it + 1)
         steps = (it + 1 - first) * args.envs * args.horizon
-        print("iter %3d  env-steps %11d  %.0f env-steps/s incl. learning  return per member: %s"
-              % (it, steps, steps / (time.perf_counter() - t0), " ".join("%7.1f" % (r * env.max_steps) for r in s["mean_step_reward"])))
+        print("iter %3d  env-steps %11d  %.0f env-steps/s incl. learning  return per member: %s%s"
+              % (it, steps, steps / (time.perf_counter() - t0), " ".join("%7.1f" % (r * env.max_steps) for r in s["mean_step_reward"]), pbt))
+    if args.curve:
+        import json
+        curve["hyper_at_end"] = pop.hypers()
+        with open(args.curve, "w") as f:
+            json.dump(curve, f, indent=1)
     if args.save:
         torch.save([p.state_dict() for p in pop.policies], args.save)
 

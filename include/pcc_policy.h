@@ -104,6 +104,31 @@ int pcc_ppo_minibatch_step_pop(const float *obs, const float *act, const float *
 int pcc_gae_pop(const float *rewards, const float *values, const uint8_t *dones, const float *last_value, int T,
                 int64_t n_envs, int n_members, const float *hyper, float *adv_out, float *ret_out, void *stream);
 
+/*
+ * The step between two generations of a population (population-based training, Jaderberg et al. 2017: truncation selection,
+ * copy, perturb) on the blocks above, ONE launch, no copy to the host, nothing synchronizes.  Arch-agnostic: it takes n_params.
+ * score     [n_members] float64, larger is better
+ * explore   [8][4] floats, one row per column of hyper: {factor_lo, factor_hi, min, max}
+ * parent_out, rank_out   [n_members] int32; either may be NULL
+ * Ordering: member a is better than b (a != b) when exactly one of the two scores is NaN and a's is not; else when neither is
+ * NaN, score[a] != score[b] and score[a] > score[b]; else when a < b.  rank[m] = the number of members better than m: a
+ * permutation of 0 .. n_members - 1, ties and +-0 broken by index, NaN last.
+ * With n_valid the number of non-NaN scores and n_src = min(n_cut, n_valid), member m is replaced iff n_src > 0 and
+ * rank[m] >= n_members - n_cut.  Its source: w = philox4x32_10(counter (m, generation, 0, 0), key (seed & 0xffffffff, seed >> 32)),
+ * j = ((uint64)w[0] * n_src) >> 32, p = the member of rank j.  Sources have rank < n_src <= n_cut <= n_members / 2: no row is
+ * both read and written.  The floats [0, n_params) of row p of params, adam_m and adam_v are copied to row m (the padding is
+ * never read or written); hyper[m][c] = fminf(fmaxf(hyper[p][c] * f, explore[c][2]), explore[c][3]) for every column c, one
+ * float32 multiply, f = explore[c][1] if bit c of w[1] is set, else explore[c][0] -- a row {1, 1, -inf, +inf} inherits the
+ * value exactly; parent_out[m] = p.  Of a member that is not replaced nothing is written, and parent_out[m] = m.
+ * rank_out[m] = rank[m] for every m.  The same arguments on the same inputs give the same bits.
+ * Returns 0; -1, with nothing written and before any device call, for n_members outside 1 .. 1024, n_cut < 0 or 2 n_cut >
+ * n_members, param_stride not a multiple of 64, n_params < 1 or > param_stride, a NULL score / params / adam_m / adam_v /
+ * hyper / explore; -3 launch failure.
+ */
+int pcc_pbt_evolve(const double *score, int n_members, int n_cut, float *params, float *adam_m, float *adam_v,
+                   int64_t param_stride, int64_t n_params, float *hyper, const float *explore, uint64_t seed,
+                   uint32_t generation, int32_t *parent_out, int32_t *rank_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

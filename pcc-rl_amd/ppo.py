@@ -469,6 +469,25 @@ def normalise_per_member(adv, n_members):
 
 
 HYPER_COLS = 8   # a row of `hyper` (include/pcc_policy.h): {lr, clip, ent_coef, gamma, lam, 0, 0, 0}
+HYPER_NAMES = ("lr", "clip", "ent_coef", "gamma", "lam")   # the columns PopulationPPO.evolve can perturb or bound, by name
+
+
+def explore_matrix(factors=(0.8, 1.2), explore=("lr", "ent_coef"), bounds=None):
+    """The [8][4] rows {factor_lo, factor_hi, min, max} pcc_pbt_evolve takes (include/pcc_policy.h), as a list: the columns
+    named in `explore` get `factors`, every other column -- the three reserved ones too -- {1, 1, -inf, +inf}, which inherits
+    the parent's value unchanged; bounds: {name: (lo, hi)}."""
+    inf = float("inf")
+    rows = [[1.0, 1.0, -inf, inf] for _ in range(HYPER_COLS)]
+    lo, hi = float(factors[0]), float(factors[1])
+    for name in explore:
+        if name not in HYPER_NAMES:
+            raise ValueError("evolve: no hyper-parameter %r (one of %s)" % (name, ", ".join(HYPER_NAMES)))
+        rows[HYPER_NAMES.index(name)][:2] = [lo, hi]
+    for name, b in (bounds or {}).items():
+        if name not in HYPER_NAMES:
+            raise ValueError("evolve: bounds for %r, which is no hyper-parameter (one of %s)" % (name, ", ".join(HYPER_NAMES)))
+        rows[HYPER_NAMES.index(name)][2:] = [float(b[0]), float(b[1])]
+    return rows
 
 
 class PopulationPPO(object):
@@ -516,6 +535,7 @@ class PopulationPPO(object):
         dev = env.device
         self.hyper_rows = [list(r) + [0.0] * (HYPER_COLS - 5) for r in zip(*cols)]
         self.hyper = torch.tensor(self.hyper_rows, dtype=torch.float32, device=dev)
+        self.generation = 0   # evolve() calls so far: the Philox counter of the next one
         D = int(env.obs_dim)
         self.n_params = 2 * (self.arch[0] * D + self.arch[0] + self.arch[1] * self.arch[0] + 2 * self.arch[1] + 1) + 1
         self.param_stride = (self.n_params + 63) // 64 * 64   # every member's block 256-byte aligned
@@ -625,13 +645,44 @@ class PopulationPPO(object):
         stats["mean_step_reward"] = rew.reshape(rew.shape[0], self.members, self.n_member).mean(dim=(0, 2)).tolist()
         return stats
 
+    def evolve(self, scores, frac=0.25, factors=(0.8, 1.2), explore=("lr", "ent_coef"), bounds=None, seed=0):
+        """The step between two generations of population-based training, one launch (pcc_pbt_evolve, include/pcc_policy.h): the
+        n_cut = int(frac * members) members with the lowest `scores` (K numbers or a tensor, larger is better, NaN last) each
+        take over the parameters, Adam's moments and the hyper-parameters of a member drawn from the best n_cut, and the
+        hyper-parameters named in `explore` are multiplied by one of the two `factors` and clamped to `bounds` ({name: (lo, hi)}).
+        The draws are Philox's of (seed, self.generation, member): a run repeats and resumes bit for bit.  Returns (parent, rank)
+        as device int32 tensors -- parent[m] == m for a member that was not replaced -- without synchronising.  The host mirror
+        hyper_rows is stale from here on (None): hypers() reads the rows back."""
+        from .native import lib
+        if not 0.0 <= frac <= 0.5:
+            raise ValueError("evolve: frac = %r (0 .. 0.5: the worst members are replaced from as many of the best)" % (frac,))
+        dev = self.env.device
+        score = torch.as_tensor(scores).detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
+        if score.numel() != self.members:
+            raise ValueError("evolve: %d scores for %d members" % (score.numel(), self.members))
+        ex = torch.tensor(explore_matrix(factors, explore, bounds), dtype=torch.float32, device=dev)
+        parent = torch.empty(self.members, dtype=torch.int32, device=dev)
+        rank = torch.empty(self.members, dtype=torch.int32, device=dev)
+        rc = lib().pcc_pbt_evolve(_ptr(score), self.members, int(frac * self.members), _ptr(self.flat), _ptr(self.adam_m), _ptr(self.adam_v),
+                                  self.param_stride, self.n_params, _ptr(self.hyper), _ptr(ex), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                  self.generation & 0xFFFFFFFF, _ptr(parent), _ptr(rank), self._stream())
+        if rc != 0:
+            raise RuntimeError("pcc_pbt_evolve failed (%d)" % rc)
+        self.generation += 1
+        self.hyper_rows = None
+        return parent, rank
+
+    def hypers(self):
+        """Every member's hyper row as the device holds it now ([members][8] floats, a list).  A synchronise: for logging."""
+        return self.hyper.tolist()
+
     def state_dict(self):
         """Everything the next iterate() depends on (PPO.state_dict's contract): the flat block, Adam's state and step, hyper, the
-        observation, the generator states and the env's snapshot."""
+        observation, the generator states and the env's snapshot; and the generation the next evolve() draws with."""
         dev = torch.device(self.env.device)
         return {"format": "population-1", "members": self.members, "obs_dim": int(self.env.obs_dim), "n_envs": int(self.env.n_envs),
                 "arch": self.arch, "flat": self.flat.detach().clone(), "adam_m": self.adam_m.clone(), "adam_v": self.adam_v.clone(),
-                "adam_t": int(self.adam_t), "hyper": self.hyper.clone(), "obs": self.obs.detach().clone(),
+                "adam_t": int(self.adam_t), "generation": int(self.generation), "hyper": self.hyper.clone(), "obs": self.obs.detach().clone(),
                 "torch_rng": torch.get_rng_state(), "device_rng": torch.cuda.get_rng_state(dev), "env": self.env.snapshot()}
 
     def load_state_dict(self, sd):
@@ -651,6 +702,7 @@ class PopulationPPO(object):
             self.hyper.copy_(sd["hyper"])
         self.hyper_rows = [[float(x) for x in r] for r in self.hyper.tolist()]
         self.adam_t = int(sd["adam_t"])
+        self.generation = int(sd.get("generation", 0))   # (a checkpoint from before evolve() has none)
         self.obs = sd["obs"].to(dev).clone()
         torch.set_rng_state(sd["torch_rng"].cpu())
         torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)

@@ -16,6 +16,8 @@
 // the gradient kernel runs ONE network per pass (policy, then value: the observation rows are gathered twice) -- both networks'
 // accumulators (384) plus a tile's activations do not fit the 512 registers of a wavefront.
 // LDS at (128; 64, 64): weights 12 612 floats + 8 416 per wavefront; 160 KiB hold three wavefronts (four in the other classes).
+// Both kernels serve the stand-alone and the population entry points: the member is one more grid dimension (one member, zero
+// strides and hyper == NULL in a stand-alone call), and the translation units pcc_mlp_tiles_d32/d64/d128.hip hold all of them.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -301,12 +303,22 @@ __device__ __forceinline__ void acc_store(const GradAcc<H1P, H2P, DP> &g, float 
 // same objective, masks and statistics; pass 0 = the policy network (+ log_std, statistics 0 and 2), pass 1 = the value network
 // (statistic 1).  Every workgroup writes ONE partial gradient (2 n_net + 1 parameters + 4 statistics): its wavefronts' sums are
 // added in the weight area in wavefront order once the pass's tiles are done.  No atomics: deterministic.
+// blockIdx.y = member of a population, as in ppo_grad_mfma_kernel (one member, hyper == NULL and perm_all possibly NULL in a
+// stand-alone call): its permutation row, parameter block, clip (hyper[m][1]) and slice of the partial-gradient scratch.
 // ======================================================================================
 template <int DP, int H1P, int H2P>
 __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void ppo_grad_tiled_kernel(
     const float *__restrict__ obs, const float *__restrict__ act, const float *__restrict__ logp_old,
-    const float *__restrict__ adv, const float *__restrict__ ret, const int64_t *__restrict__ perm, int64_t start,
-    int64_t count, int D, int n_h1, int n_h2, const float *__restrict__ params, float clip, float *__restrict__ partial) {
+    const float *__restrict__ adv, const float *__restrict__ ret, const int64_t *__restrict__ perm_all, int64_t perm_stride,
+    int64_t start, int64_t count, int D, int n_h1, int n_h2, const float *__restrict__ params_all, int64_t param_stride,
+    const float *__restrict__ hyper, float clip_arg, float *__restrict__ partial_all, int64_t partial_stride) {
+    const int64_t member = blockIdx.y;
+    const int64_t *perm = perm_all ? perm_all + member * perm_stride : nullptr;
+    const float *params = params_all + member * param_stride;
+    float *partial = partial_all + member * partial_stride;
+    float clip = hyper ? hyper[member * 8 + 1] : clip_arg;
+    // (the member's pointers are made here, once, in scalar registers: left to the scheduler, (128; 64, 32) spills six vector registers)
+    asm volatile("" : "+s"(perm), "+s"(params), "+s"(partial), "+s"(clip));
     using C = Cls<DP, H1P, H2P>;
     constexpr int kWaves = C::kWaves;
     __shared__ float lds[C::kLds];
@@ -415,12 +427,19 @@ __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void ppo_grad_
 // policy_act_tiled_kernel: pcc_policy_act for the shapes its older kernels refuse -- the forward above, blockIdx.y = network
 // (0: pi -> mean, action, log-probability; 1: vf -> value) like policy_act_fixed_kernel.  A sample's result does not depend on
 // where in a tile or batch it sits (each row of an MFMA result is that row's own fmaf chain).
+// blockIdx.z = member of a population (one in a stand-alone call): n = the member's rows, which it sees with its parameter block
+// through offset pointers -- tiles start at the member's first row, as in a stand-alone launch over them.
 // ======================================================================================
 template <int DP, int H1P, int H2P>
 __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void policy_act_tiled_kernel(
-    const float *__restrict__ obs, int64_t n, int D, int n_h1, int n_h2, const float *__restrict__ params,
-    const float *__restrict__ noise, float *__restrict__ mean_out, float *__restrict__ act_out, float *__restrict__ logp_out,
-    float *__restrict__ value_out) {
+    const float *__restrict__ obs_all, int64_t n, int D, int n_h1, int n_h2, const float *__restrict__ params_all, int64_t param_stride,
+    const float *__restrict__ noise_all, float *__restrict__ mean_all, float *__restrict__ act_all, float *__restrict__ logp_all,
+    float *__restrict__ value_all) {
+    const int64_t member = blockIdx.z, off = member * n;
+    const float *__restrict__ obs = obs_all + off * D, *__restrict__ params = params_all + member * param_stride;
+    const float *__restrict__ noise = noise_all ? noise_all + off : nullptr;
+    float *__restrict__ mean_out = mean_all ? mean_all + off : nullptr, *__restrict__ act_out = act_all ? act_all + off : nullptr;
+    float *__restrict__ logp_out = logp_all ? logp_all + off : nullptr, *__restrict__ value_out = value_all ? value_all + off : nullptr;
     using C = Cls<DP, H1P, H2P>;
     constexpr int kWaves = C::kWaves;
     __shared__ float lds[C::kLds];
@@ -454,21 +473,29 @@ __global__ __launch_bounds__((Cls<DP, H1P, H2P>::kWaves) * 64, 1) void policy_ac
     }
 }
 
-// ---- host side: one translation unit per DP (pcc_mlp_tiles_d*.hip) instantiates its three hidden classes
+// ---- host side: one translation unit per DP (pcc_mlp_tiles_d*.hip) instantiates its three hidden classes.  The argument blocks
+// serve the stand-alone entry points (n_members = 1, strides 0, hyper NULL) and the population's.
 struct GradArgs {
     const float *obs, *act, *logp_old, *adv, *ret;
-    const int64_t *perm;
-    int64_t start, count;
+    const int64_t *perm;     // member 0's row (may be NULL: the samples in order)
+    int64_t perm_stride, start, count;
     int D, h1, h2;
-    const float *params;
+    const float *params;     // member 0's block
+    int64_t param_stride;
+    const float *hyper;      // [n_members][8] on the device, or NULL: `clip` below
     float clip;
-    float *partial;
+    float *partial;          // member 0's slice of the scratch
+    int64_t partial_stride;
+    int n_members;
 };
-struct ActArgs {
+struct ActArgs {             // n = a member's rows; every row pointer is the whole batch's
     const float *obs;
     int64_t n;
     int D, h1, h2;
-    const float *params, *noise;
+    const float *params;
+    int64_t param_stride;
+    int n_members;
+    const float *noise;
     float *mean_out, *act_out, *logp_out, *value_out;
 };
 
@@ -480,8 +507,9 @@ inline int launch_class(const GradArgs &a, hipStream_t st, int *blocks_out) {
     int64_t blocks = (tiles + C::kWaves - 1) / C::kWaves;
     if (blocks > kMaxGradBlocks) blocks = kMaxGradBlocks;
     *blocks_out = (int)blocks;
-    hipLaunchKernelGGL((ppo_grad_tiled_kernel<DP, H1P, H2P>), dim3((unsigned)blocks), dim3(C::kWaves * kWave), 0, st, a.obs, a.act,
-                       a.logp_old, a.adv, a.ret, a.perm, a.start, a.count, a.D, a.h1, a.h2, a.params, a.clip, a.partial);
+    hipLaunchKernelGGL((ppo_grad_tiled_kernel<DP, H1P, H2P>), dim3((unsigned)blocks, (unsigned)a.n_members), dim3(C::kWaves * kWave), 0, st,
+                       a.obs, a.act, a.logp_old, a.adv, a.ret, a.perm, a.perm_stride, a.start, a.count, a.D, a.h1, a.h2, a.params,
+                       a.param_stride, a.hyper, a.clip, a.partial, a.partial_stride);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -491,8 +519,8 @@ inline int launch_class(const ActArgs &a, hipStream_t st, int *) {
     const int64_t tiles = (a.n + kTile - 1) / kTile;
     int64_t blocks = (tiles + C::kWaves - 1) / C::kWaves;
     if (blocks > 128) blocks = 128;   // (a workgroup stages the weights once and walks its tiles; 2 x 128 = one per CU)
-    hipLaunchKernelGGL((policy_act_tiled_kernel<DP, H1P, H2P>), dim3((unsigned)blocks, 2), dim3(C::kWaves * kWave), 0, st, a.obs, a.n,
-                       a.D, a.h1, a.h2, a.params, a.noise, a.mean_out, a.act_out, a.logp_out, a.value_out);
+    hipLaunchKernelGGL((policy_act_tiled_kernel<DP, H1P, H2P>), dim3((unsigned)blocks, 2, (unsigned)a.n_members), dim3(C::kWaves * kWave), 0,
+                       st, a.obs, a.n, a.D, a.h1, a.h2, a.params, a.param_stride, a.noise, a.mean_out, a.act_out, a.logp_out, a.value_out);
     return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

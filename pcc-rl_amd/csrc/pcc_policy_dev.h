@@ -29,8 +29,8 @@ static_assert(PolicyLayout(30, 32, 16).B1 == 960 && PolicyLayout(30, 32, 16).W2 
 static_assert(PolicyLayout(7, 5, 3).vf() == PolicyLayout(7, 5, 3).log_std() + 1 && PolicyLayout(1, 1, 1).n_params() == 13, "pi, log_std, vf");
 
 // The observation lengths with a fully unrolled kernel for the reference's --arch 32,16: policy_act_fixed_kernel<D, 32, 16> (and
-// the older policy_act_kernel<D> for other small policies) at all of them, ppo_grad_mfma_kernel<D, 32, 16> at those of at most
-// 32 observations.  Every dispatch is generated from these lists; pcc_rollout runs --arch 32,16 at these lengths only.
+// the generic policy_act_kernel<D> for other small policies) at all of them, ppo_grad_mfma_kernel<D, 32, 16> at those of at most
+// 32 observations -- each ONE kernel for the stand-alone and the population entry points (the member is a grid dimension).  Every dispatch is generated from these lists; pcc_rollout runs --arch 32,16 at these lengths only.
 #define PCC_MFMA_OBS_LENGTHS(X) X(30) X(3) X(6) X(12)   // 30 = history 10 x 3 features: the reference's default observation (ns:382-388)
 #define PCC_FIXED_OBS_LENGTHS(X) PCC_MFMA_OBS_LENGTHS(X) X(36) X(60)   // 36 = history 3 x all 12 features
 #define PCC_FIXED_OBS_LENGTHS_TEXT "3, 6, 12, 30, 36 or 60"             // (the same lengths, for messages)

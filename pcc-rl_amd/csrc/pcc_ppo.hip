@@ -23,11 +23,15 @@
 //
 // Plus the GAE recursion as one launch (thread = env, T steps backwards).  fp32 like the framework path; checked against
 // torch autograd in tests/test_ppo.py.
+//
+// Every kernel's grid has a member dimension: pcc_ppo_minibatch_step / pcc_gae are pcc_ppo_minibatch_step_pop / pcc_gae_pop with one
+// member (include/pcc_policy.h), through the same launch functions (launch_step, launch_gae).  What a stand-alone call has on the
+// host -- clip, lr, ent_coef, gamma, lam -- is a kernel argument, read where the population's device array `hyper` is NULL.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
-#include "pcc_mlp_tiles_pop.h"
+#include "pcc_mlp_tiles.h"
 #include "pcc_policy.h"
 
 namespace {
@@ -224,136 +228,21 @@ __device__ __forceinline__ void mfma_acc_store(const MfmaAcc &acc, float *g, con
     if (lane == 0u) put(L.B3, b3);
 }
 
-// ppo_grad_mfma_kernel's statements (below) as the body of its population twin, ppo_grad_mfma_pop_kernel: a copy, kept in step by
-// hand and held against the original bit for bit by tests/test_population.py -- called from the old kernel too, the body changes
-// that kernel's schedule.
-template <int D, int H1, int H2>
-__device__ __forceinline__ void ppo_grad_mfma_body(const float *__restrict__ obs, const float *__restrict__ act, const float *__restrict__ logp_old, const float *__restrict__ adv,
-                                                   const float *__restrict__ ret, const int64_t *__restrict__ perm, int64_t start, int64_t count,
-                                                   const float *__restrict__ params, float clip, float *__restrict__ partial) {
-    constexpr PolicyLayout L(D, H1, H2);
-    static_assert(H1 == 32 && H2 == 16 && D <= 32, "the MFMA tiles are the reference's --arch 32,16 on at most 32 features");
-    constexpr int kPi = 0, kLogStd = L.log_std(), kVf = L.vf(), kParams = L.n_params();
-    static_assert(kParams + 4 <= kMfmaWaveLds, "the block's gradient is reduced in a wavefront's LDS buffers");
-    __shared__ float lds[kWavesPerBlock * kMfmaWaveLds];
-    const uint32_t lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-    float *Xs = lds + wv * kMfmaWaveLds, *H1s = Xs + kBufFloats, *Zs = H1s + kBufFloats, *Sc = Zs + kBufFloats;
-    const float log_std = params[kLogStd];
-    const float inv_std = __expf(-log_std);
-    const float inv_n = 1.0f / (float)count;
-    // both networks' weights stay in registers (~480 with the activations of a tile: one wavefront per SIMD.  One network
-    // at a time -- two passes over the samples, two wavefronts per SIMD at 256 registers -- was measured: 506 us against
-    // 328 per million samples, spills and a second gather of the observation rows)
-    MfmaWeights wpi, wvf;
-    mfma_load_weights<D, H1, H2>(wpi, params + kPi, lane);
-    mfma_load_weights<D, H1, H2>(wvf, params + kVf, lane);
-    MfmaAcc gpi, gvf;
-#pragma unroll
-    for (int r = 0; r < 16; r++) { gpi.w1[r] = 0.0f; gvf.w1[r] = 0.0f; }
-#pragma unroll
-    for (int r = 0; r < 4; r++) { gpi.w2a[r] = gpi.w2b[r] = 0.0f; gvf.w2a[r] = gvf.w2b[r] = 0.0f; }
-    gpi.b1 = gpi.b2 = gpi.w3 = gpi.b3 = 0.0f;
-    gvf.b1 = gvf.b2 = gvf.w3 = gvf.b3 = 0.0f;
-    float g_logstd = 0.0f, s_pg = 0.0f, s_vf = 0.0f, s_clip = 0.0f;
-    const int64_t n_tiles = (count + kWave - 1) / kWave;
-    for (int64_t tile = (int64_t)blockIdx.x * kWavesPerBlock + wv; tile < n_tiles; tile += (int64_t)gridDim.x * kWavesPerBlock) {
-        // ---- the tile's samples, sample-major in LDS (lane = sample for the loads only)
-        {
-            const int64_t k = tile * kWave + lane;
-            const bool valid = k < count;
-            const int64_t idx = valid ? (perm ? perm[start + k] : start + k) : 0;
-            if constexpr (D % 2 == 0) {
-                const float2 *row = reinterpret_cast<const float2 *>(obs + idx * D);   // D even: 8-byte aligned rows
-#pragma unroll
-                for (int j = 0; j < D / 2; j++) {
-                    const float2 v = row[j];
-                    Xs[lane * kS33 + 2 * j] = valid ? v.x : 0.0f;
-                    Xs[lane * kS33 + 2 * j + 1] = valid ? v.y : 0.0f;
-                }
-            } else {
-#pragma unroll
-                for (int j = 0; j < D; j++) Xs[lane * kS33 + j] = valid ? obs[idx * D + j] : 0.0f;
-            }
-#pragma unroll
-            for (int j = D; j < 32; j++) Xs[lane * kS33 + j] = 0.0f;
-            Sc[lane] = valid ? act[idx] : 0.0f;
-            Sc[kWave + lane] = valid ? logp_old[idx] : 0.0f;
-            Sc[2 * kWave + lane] = valid ? adv[idx] : 0.0f;
-            Sc[3 * kWave + lane] = valid ? ret[idx] : 0.0f;
-        }
-        __builtin_amdgcn_wave_barrier();
-        const int64_t left = count - tile * kWave;   // samples of this tile that exist
-        float h1[2][16], h2[4][4], out[4][4], dout[4][4];
-        // ---- policy network: log-probability of the taken action, clipped surrogate.  The per-sample arithmetic below is
-        // written out in ppo_grad_tiled_kernel (pcc_mlp_tiles.h) too and the two are kept in step by hand: as one shared
-        // function (sums by reference) the results are the same but two tiled instantiations change their register counts.
-        mfma_forward<D, H1, H2>(wpi, Xs, H1s, lane, h1, h2, out);
-#pragma unroll
-        for (int T4 = 0; T4 < 4; T4++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const uint32_t m = 16u * T4 + 4u * (lane >> 4) + (uint32_t)r;
-                const bool valid = (int64_t)m < left;
-                const float a = Sc[m], lp_old = Sc[kWave + m], ad = Sc[2 * kWave + m];
-                const float z = (a - out[T4][r]) * inv_std;
-                const float lp = pcc::gaussian_logp(z, log_std);
-                const float ratio = __expf(lp - lp_old);
-                const float lo = 1.0f - clip, hi = 1.0f + clip;
-                const float rc = fminf(fmaxf(ratio, lo), hi);
-                const float surr1 = ratio * ad, surr2 = rc * ad;
-                const bool through = surr1 <= surr2;   // min picks the unclipped term (inside the range both are the same)
-                const float dlp = (valid && through) ? -ad * ratio * inv_n : 0.0f;
-                dout[T4][r] = dlp * z * inv_std;
-                if (valid && (lane & 15u) == 0u) {   // (the 16 lanes of a row hold the same sample: one of them counts)
-                    g_logstd += dlp * (z * z - 1.0f);
-                    s_pg += fminf(surr1, surr2);
-                    s_clip += (ratio < lo || ratio > hi) ? 1.0f : 0.0f;
-                }
-            }
-        }
-        mfma_backward<D, H1, H2>(wpi, gpi, Xs, H1s, Zs, lane, h1, h2, dout);
-        // ---- value network: 0.5 * mean((v - ret)^2)
-        mfma_forward<D, H1, H2>(wvf, Xs, H1s, lane, h1, h2, out);
-#pragma unroll
-        for (int T4 = 0; T4 < 4; T4++) {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const uint32_t m = 16u * T4 + 4u * (lane >> 4) + (uint32_t)r;
-                const bool valid = (int64_t)m < left;
-                const float err = valid ? out[T4][r] - Sc[3 * kWave + m] : 0.0f;
-                dout[T4][r] = err * inv_n;
-                if ((lane & 15u) == 0u) s_vf += err * err;
-            }
-        }
-        mfma_backward<D, H1, H2>(wvf, gvf, Xs, H1s, Zs, lane, h1, h2, dout);
-    }
-    // ---- the block's partial gradient: every wavefront's sums -> LDS (wavefront 0's buffers), one after the other
-    __syncthreads();
-    float *g = lds;
-    for (uint32_t w = 0; w < (uint32_t)kWavesPerBlock; w++) {
-        if (wv == w) {
-            mfma_acc_store<D, H1, H2>(gpi, g + kPi, lane, w != 0);
-            mfma_acc_store<D, H1, H2>(gvf, g + kVf, lane, w != 0);
-            const float gl = wave_sum(g_logstd), a = wave_sum(s_pg), b = wave_sum(s_vf), c = wave_sum(s_clip);
-            if (lane == 0) {
-                g[kLogStd] = (w ? g[kLogStd] : 0.0f) + gl;
-                g[kParams + 0] = (w ? g[kParams + 0] : 0.0f) + a;
-                g[kParams + 1] = (w ? g[kParams + 1] : 0.0f) + b;
-                g[kParams + 2] = (w ? g[kParams + 2] : 0.0f) + c;
-                g[kParams + 3] = 0.0f;
-            }
-        }
-        __syncthreads();
-    }
-    float *out_p = partial + (int64_t)blockIdx.x * (kParams + 4);
-    for (int k = threadIdx.x; k < kParams + 4; k += blockDim.x) out_p[k] = g[k];
-}
-
+// blockIdx.y = member of a population (a stand-alone call is a population of one: pcc_ppo_minibatch_step launches gridDim.y = 1 with
+// hyper == NULL and its clip as an argument).  Member m works on its own permutation row (perm_all may be NULL: the samples in
+// order), parameter block, clip (hyper[m][1]) and slice of the partial-gradient scratch; gridDim.x depends on `count` alone, so
+// every wavefront walks the same tiles and every sum has the same order whatever the number of members: the same bits.
 template <int D, int H1, int H2>
 __global__ __launch_bounds__(kWavesPerBlock *kWave, 1) void ppo_grad_mfma_kernel(
     const float *__restrict__ obs, const float *__restrict__ act, const float *__restrict__ logp_old,
-    const float *__restrict__ adv, const float *__restrict__ ret, const int64_t *__restrict__ perm, int64_t start,
-    int64_t count, const float *__restrict__ params, float clip, float *__restrict__ partial) {
+    const float *__restrict__ adv, const float *__restrict__ ret, const int64_t *__restrict__ perm_all, int64_t perm_stride,
+    int64_t start, int64_t count, const float *__restrict__ params_all, int64_t param_stride, const float *__restrict__ hyper,
+    float clip_arg, float *__restrict__ partial_all, int64_t partial_stride) {
+    const int64_t member = blockIdx.y;
+    const int64_t *__restrict__ perm = perm_all ? perm_all + member * perm_stride : nullptr;
+    const float *__restrict__ params = params_all + member * param_stride;
+    float *__restrict__ partial = partial_all + member * partial_stride;
+    const float clip = hyper ? hyper[member * 8 + 1] : clip_arg;
     constexpr PolicyLayout L(D, H1, H2);
     static_assert(H1 == 32 && H2 == 16 && D <= 32, "the MFMA tiles are the reference's --arch 32,16 on at most 32 features");
     constexpr int kPi = 0, kLogStd = L.log_std(), kVf = L.vf(), kParams = L.n_params();
@@ -470,62 +359,25 @@ __global__ __launch_bounds__(kWavesPerBlock *kWave, 1) void ppo_grad_mfma_kernel
     }
     float *out_p = partial + (int64_t)blockIdx.x * (kParams + 4);
     for (int k = threadIdx.x; k < kParams + 4; k += blockDim.x) out_p[k] = g[k];
-}
-
-// The gradient launch of pcc_ppo_minibatch_step_pop: blockIdx.y = member.  Member m runs the body above on its own permutation
-// row, parameter block, clip (hyper[m][1]) and slice of the partial-gradient scratch; gridDim.x is what a stand-alone call with
-// the same `count` launches, so every wavefront walks the same tiles and every sum has the same order: the same bits.
-template <int D, int H1, int H2>
-__global__ __launch_bounds__(kWavesPerBlock *kWave, 1) void ppo_grad_mfma_pop_kernel(
-    const float *__restrict__ obs, const float *__restrict__ act, const float *__restrict__ logp_old,
-    const float *__restrict__ adv, const float *__restrict__ ret, const int64_t *__restrict__ perm, int64_t perm_stride,
-    int64_t start, int64_t count, const float *__restrict__ params, int64_t param_stride, const float *__restrict__ hyper,
-    float *__restrict__ partial, int64_t partial_stride) {
-    const int64_t m = blockIdx.y;
-    ppo_grad_mfma_body<D, H1, H2>(obs, act, logp_old, adv, ret, perm + m * perm_stride, start, count, params + m * param_stride,
-                                  hyper[m * 8 + 1], partial + m * partial_stride);
-}
-
-// ppo_adam_kernel's statements (below) as the body of ppo_adam_pop_kernel: a copy for the same reason
-__device__ __forceinline__ void ppo_adam_body(const float *__restrict__ partial, int n_blocks, int n_params, int logstd_index, float ent_coef,
-                                              float *__restrict__ params, float *__restrict__ m, float *__restrict__ v, float lr, float beta1, float beta2, float eps,
-                                              float bias1, float bias2_sqrt, float inv_count, float *__restrict__ grad_out, float *__restrict__ stats_out) {
-    __shared__ float rows[16][17];
-    const int c = threadIdx.x & 15, r = threadIdx.x >> 4;
-    const int p = blockIdx.x * 16 + c;
-    const int stride = n_params + 4;
-    float g = 0.0f;
-    if (p < stride)
-        for (int b = r; b < n_blocks; b += 16) g += partial[(int64_t)b * stride + p];
-    rows[r][c] = g;
-    __syncthreads();
-    if (r != 0 || p >= stride) return;
-    g = rows[0][c];
-#pragma unroll
-    for (int k = 1; k < 16; k++) g += rows[k][c];
-    if (p >= n_params) {   // {-policy loss, 2 * value loss, clipped fraction, -} as means over the minibatch
-        if (stats_out) stats_out[p - n_params] = g * inv_count;
-        return;
-    }
-    if (p == logstd_index) g -= ent_coef;
-    if (grad_out) grad_out[p] = g;
-    if (lr == 0.0f) return;   // gradient only
-    const float mm = beta1 * m[p] + (1.0f - beta1) * g;
-    const float vv = beta2 * v[p] + (1.0f - beta2) * g * g;
-    m[p] = mm;
-    v[p] = vv;
-    const float denom = sqrtf(vv) / bias2_sqrt + eps;
-    params[p] -= (lr / bias1) * (mm / denom);
 }
 
 // 16 parameters per workgroup: thread (r, c) sums parameter c's partial gradients of the blocks r, r + 16, ..., the 16 row sums
 // are added in order (deterministic: no atomics anywhere); then the entropy term (entropy of the diagonal Gaussian = const +
-// log_std: d/d log_std of -ent_coef * entropy is -ent_coef) and Adam as torch.optim.Adam computes it.
-__global__ __launch_bounds__(256) void ppo_adam_kernel(const float *__restrict__ partial, int n_blocks, int n_params,
-                                                       int logstd_index, float ent_coef, float *__restrict__ params,
-                                                       float *__restrict__ m, float *__restrict__ v, float lr, float beta1,
-                                                       float beta2, float eps, float bias1, float bias2_sqrt, float inv_count,
-                                                       float *__restrict__ grad_out, float *__restrict__ stats_out) {
+// log_std: d/d log_std of -ent_coef * entropy is -ent_coef) and Adam as torch.optim.Adam computes it.  blockIdx.y = member, with
+// its lr and entropy coefficient from hyper[m] (hyper == NULL: the stand-alone call's arguments); the bias corrections are the
+// host's (one adam_step for all members; a member with lr == 0 returns before it reads them, and its moments may be NULL).
+__global__ __launch_bounds__(256) void ppo_adam_kernel(const float *__restrict__ partial_all, int64_t partial_stride, int n_blocks,
+                                                       int n_params, int logstd_index, const float *__restrict__ hyper,
+                                                       float ent_coef_arg, float lr_arg, float *__restrict__ params_all,
+                                                       float *__restrict__ m_all, float *__restrict__ v_all, int64_t param_stride,
+                                                       float beta1, float beta2, float eps, float bias1, float bias2_sqrt,
+                                                       float inv_count, float *__restrict__ grad_all, float *__restrict__ stats_all) {
+    const int64_t mb = blockIdx.y, po = mb * param_stride;
+    const float *__restrict__ partial = partial_all + mb * partial_stride;
+    float *__restrict__ params = params_all + po;
+    float *__restrict__ m = m_all ? m_all + po : nullptr, *__restrict__ v = v_all ? v_all + po : nullptr;
+    float *__restrict__ grad_out = grad_all ? grad_all + po : nullptr, *__restrict__ stats_out = stats_all ? stats_all + mb * 4 : nullptr;
+    const float lr = hyper ? hyper[mb * 8 + 0] : lr_arg, ent_coef = hyper ? hyper[mb * 8 + 2] : ent_coef_arg;
     __shared__ float rows[16][17];
     const int c = threadIdx.x & 15, r = threadIdx.x >> 4;
     const int p = blockIdx.x * 16 + c;
@@ -554,49 +406,16 @@ __global__ __launch_bounds__(256) void ppo_adam_kernel(const float *__restrict__
     params[p] -= (lr / bias1) * (mm / denom);
 }
 
-// The Adam launch of pcc_ppo_minibatch_step_pop: blockIdx.y = member, with its lr and entropy coefficient from hyper[m]; the bias
-// corrections are the host's (one adam_step for all members; a member with lr == 0 returns before it reads them).
-__global__ __launch_bounds__(256) void ppo_adam_pop_kernel(const float *__restrict__ partial, int64_t partial_stride, int n_blocks,
-                                                           int n_params, int logstd_index, const float *__restrict__ hyper,
-                                                           float *__restrict__ params, float *__restrict__ m, float *__restrict__ v,
-                                                           int64_t param_stride, float beta1, float beta2, float eps, float bias1,
-                                                           float bias2_sqrt, float inv_count, float *__restrict__ grad_out,
-                                                           float *__restrict__ stats_out) {
-    const int64_t mb = blockIdx.y, po = mb * param_stride;
-    ppo_adam_body(partial + mb * partial_stride, n_blocks, n_params, logstd_index, hyper[mb * 8 + 2], params + po, m + po, v + po,
-                  hyper[mb * 8 + 0], beta1, beta2, eps, bias1, bias2_sqrt, inv_count, grad_out ? grad_out + po : nullptr,
-                  stats_out ? stats_out + mb * 4 : nullptr);
-}
-
 // Generalised advantage estimation over [T][N] rollout rows (thread = env, backwards in time): dones[t] marks that the
-// env was reset after step t.
+// env was reset after step t.  blockIdx.y = member, which owns n_member consecutive columns of the [T][n] rows and reads its
+// own gamma and lambda (hyper[m][3], [4]; hyper == NULL: the stand-alone call's arguments, one member of all n columns).
 __global__ void gae_kernel(const float *__restrict__ rew, const float *__restrict__ val, const uint8_t *__restrict__ done,
-                           const float *__restrict__ last_val, int T, int64_t n, float gamma, float lam,
-                           float *__restrict__ adv, float *__restrict__ ret) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    float next_v = last_val[i], run = 0.0f;
-    for (int t = T - 1; t >= 0; t--) {
-        const int64_t k = (int64_t)t * n + i;
-        const float alive = done[k] ? 0.0f : 1.0f;
-        const float v = val[k];
-        const float delta = rew[k] + gamma * next_v * alive - v;
-        run = delta + gamma * lam * alive * run;
-        adv[k] = run;
-        ret[k] = run + v;
-        next_v = v;
-    }
-}
-
-// gae_kernel for a population: blockIdx.y = member, which owns n_member consecutive columns of the [T][n] rows and reads its
-// own gamma and lambda (hyper[m][3], [4]); thread = env, the same operations in the same order.
-__global__ void gae_pop_kernel(const float *__restrict__ rew, const float *__restrict__ val, const uint8_t *__restrict__ done,
-                               const float *__restrict__ last_val, int T, int64_t n, int64_t n_member, const float *__restrict__ hyper,
-                               float *__restrict__ adv, float *__restrict__ ret) {
+                           const float *__restrict__ last_val, int T, int64_t n, int64_t n_member, const float *__restrict__ hyper,
+                           float gamma_arg, float lam_arg, float *__restrict__ adv, float *__restrict__ ret) {
     const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_member) return;
     const int64_t i = (int64_t)blockIdx.y * n_member + r;
-    const float gamma = hyper[blockIdx.y * 8 + 3], lam = hyper[blockIdx.y * 8 + 4];
+    const float gamma = hyper ? hyper[blockIdx.y * 8 + 3] : gamma_arg, lam = hyper ? hyper[blockIdx.y * 8 + 4] : lam_arg;
     float next_v = last_val[i], run = 0.0f;
     for (int t = T - 1; t >= 0; t--) {
         const int64_t k = (int64_t)t * n + i;
@@ -622,6 +441,48 @@ extern "C" int pcc_ppo_scratch_floats(int obs_dim, int h1, int h2) {
     return blocks * (PolicyLayout(obs_dim, h1, h2).n_params() + 4);
 }
 
+// One optimiser step of a.n_members learners (both entry points; the arguments are checked there): the gradient launch, then the
+// Adam launch.  a.hyper != NULL: lr, clip and ent_coef are the members' rows of it and every member may update; NULL: the arguments.
+static int launch_step(pcc_tiles::GradArgs a, float *params, float *adam_m, float *adam_v, int adam_step, float lr, float beta1,
+                       float beta2, float eps, float ent_coef, float *grad_out, float *stats_out, hipStream_t st) {
+    if (!pcc_tiles::in_domain(a.D, a.h1, a.h2)) return -2;   // (the caller falls back to its framework path)
+    const PolicyLayout L(a.D, a.h1, a.h2);
+    a.partial_stride = pcc_ppo_scratch_floats(a.D, a.h1, a.h2);
+    int blocks = 0;
+    if (mfma_fixed_shape(a.D, a.h1, a.h2)) {
+        const int64_t tiles = (a.count + kWave - 1) / kWave;
+        const int64_t nb = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
+        blocks = nb > kMaxBlocks ? kMaxBlocks : (int)nb;
+        const dim3 grid((unsigned)blocks, (unsigned)a.n_members), block(kWavesPerBlock * kWave);
+#define PCC_PPO_CASE(DD)                                                                                                        \
+    if (a.D == DD)                                                                                                              \
+        hipLaunchKernelGGL((ppo_grad_mfma_kernel<DD, 32, 16>), grid, block, 0, st, a.obs, a.act, a.logp_old, a.adv, a.ret, a.perm, \
+                           a.perm_stride, a.start, a.count, a.params, a.param_stride, a.hyper, a.clip, a.partial, a.partial_stride);
+        PCC_MFMA_OBS_LENGTHS(PCC_PPO_CASE)
+#undef PCC_PPO_CASE
+    } else {   // any other shape of the domain: the tiled kernel
+        const int rc = pcc_tiles::launch_grad(a, st, &blocks);
+        if (rc != 0) return rc;
+    }
+    if (hipGetLastError() != hipSuccess) return -3;
+    const bool update = a.hyper || lr != 0.0f;
+    const float bias1 = update ? 1.0f - powf(beta1, (float)adam_step) : 1.0f;
+    const float bias2 = update ? sqrtf(1.0f - powf(beta2, (float)adam_step)) : 1.0f;
+    hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((L.n_params() + 4 + 15) / 16), (unsigned)a.n_members), dim3(256), 0, st, a.partial,
+                       a.partial_stride, blocks, L.n_params(), L.log_std(), a.hyper, ent_coef, lr, params, adam_m, adam_v, a.param_stride,
+                       beta1, beta2, eps, bias1, bias2, 1.0f / (float)a.count, grad_out, stats_out);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+static int launch_gae(const float *rewards, const float *values, const uint8_t *dones, const float *last_value, int T, int64_t n_envs,
+                      int n_members, const float *hyper, float gamma, float lam, float *adv_out, float *ret_out, void *stream) {
+    const int64_t n_member = n_envs / n_members;
+    hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((n_member + 255) / 256), (unsigned)n_members), dim3(256), 0,
+                       static_cast<hipStream_t>(stream), rewards, values, dones, last_value, T, n_envs, n_member, hyper, gamma, lam,
+                       adv_out, ret_out);
+    return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
 extern "C" int pcc_ppo_minibatch_step(const float *obs, const float *act, const float *logp_old, const float *adv,
                                       const float *ret, const int64_t *perm, int64_t start, int64_t count, int obs_dim,
                                       int h1, int h2, float *params, float *adam_m, float *adam_v, int adam_step, float lr,
@@ -629,42 +490,15 @@ extern "C" int pcc_ppo_minibatch_step(const float *obs, const float *act, const 
                                       float *grad_out, float *stats_out, void *stream) {
     if (!obs || !act || !logp_old || !adv || !ret || !params || !scratch || count < 1 || start < 0) return -1;
     if (lr != 0.0f && (!adam_m || !adam_v || adam_step < 1)) return -1;
-    const PolicyLayout L(obs_dim, h1, h2);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    int64_t blocks;
-    if (mfma_fixed_shape(obs_dim, h1, h2)) {
-        const int64_t tiles = (count + kWave - 1) / kWave;
-        blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-        if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-        const dim3 grid((unsigned)blocks), block(kWavesPerBlock * kWave);
-#define PCC_PPO_CASE(DD)                                                                                                   \
-    if (obs_dim == DD)                                                                                                     \
-        hipLaunchKernelGGL((ppo_grad_mfma_kernel<DD, 32, 16>), grid, block, 0, st, obs, act, logp_old, adv, ret, perm, start, \
-                           count, params, clip, scratch);
-        PCC_MFMA_OBS_LENGTHS(PCC_PPO_CASE)
-#undef PCC_PPO_CASE
-    } else {   // any other shape of the domain: the tiled kernel (-2 outside: the caller falls back to its framework path)
-        const pcc_tiles::GradArgs a{obs, act, logp_old, adv, ret, perm, start, count, obs_dim, h1, h2, params, clip, scratch};
-        int nb = 0;
-        const int rc = pcc_tiles::launch_grad(a, st, &nb);
-        if (rc != 0) return rc;
-        blocks = nb;
-    }
-    if (hipGetLastError() != hipSuccess) return -3;
-    const float bias1 = lr != 0.0f ? 1.0f - powf(beta1, (float)adam_step) : 1.0f;
-    const float bias2 = lr != 0.0f ? sqrtf(1.0f - powf(beta2, (float)adam_step)) : 1.0f;
-    hipLaunchKernelGGL(ppo_adam_kernel, dim3((unsigned)((L.n_params() + 4 + 15) / 16)), dim3(256), 0, st, scratch, (int)blocks,
-                       L.n_params(), L.log_std(), ent_coef, params, adam_m, adam_v, lr, beta1, beta2, eps, bias1, bias2,
-                       1.0f / (float)count, grad_out, stats_out);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    const pcc_tiles::GradArgs a{obs, act, logp_old, adv, ret, perm, 0, start, count, obs_dim, h1, h2, params, 0, nullptr, clip, scratch, 0, 1};
+    return launch_step(a, params, adam_m, adam_v, adam_step, lr, beta1, beta2, eps, ent_coef, grad_out, stats_out,
+                       static_cast<hipStream_t>(stream));
 }
 
 extern "C" int pcc_gae(const float *rewards, const float *values, const uint8_t *dones, const float *last_value, int T,
                        int64_t n_envs, float gamma, float lam, float *adv_out, float *ret_out, void *stream) {
     if (!rewards || !values || !dones || !last_value || !adv_out || !ret_out || T < 1 || n_envs < 1) return -1;
-    hipLaunchKernelGGL(gae_kernel, dim3((unsigned)((n_envs + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       rewards, values, dones, last_value, T, n_envs, gamma, lam, adv_out, ret_out);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_gae(rewards, values, dones, last_value, T, n_envs, 1, nullptr, gamma, lam, adv_out, ret_out, stream);
 }
 
 extern "C" int pcc_ppo_minibatch_step_pop(const float *obs, const float *act, const float *logp_old, const float *adv,
@@ -676,46 +510,16 @@ extern "C" int pcc_ppo_minibatch_step_pop(const float *obs, const float *act, co
     if (!adam_m || !adam_v || adam_step < 1) return -1;   // (the learning rates are on the device: every member may update)
     if (n_members < 1 || n_members > 1024 || perm_stride < 0) return -1;
     if (!pcc_tiles::in_domain(obs_dim, h1, h2)) return -2;
-    const PolicyLayout L(obs_dim, h1, h2);
-    if (param_stride < L.n_params() || param_stride % 64 != 0) return -1;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int64_t partial_stride = pcc_ppo_scratch_floats(obs_dim, h1, h2);
-    int64_t blocks;
-    if (mfma_fixed_shape(obs_dim, h1, h2)) {
-        const int64_t tiles = (count + kWave - 1) / kWave;
-        blocks = (tiles + kWavesPerBlock - 1) / kWavesPerBlock;
-        if (blocks > kMaxBlocks) blocks = kMaxBlocks;
-        const dim3 grid((unsigned)blocks, (unsigned)n_members), block(kWavesPerBlock * kWave);
-#define PCC_PPO_CASE(DD)                                                                                                       \
-    if (obs_dim == DD)                                                                                                         \
-        hipLaunchKernelGGL((ppo_grad_mfma_pop_kernel<DD, 32, 16>), grid, block, 0, st, obs, act, logp_old, adv, ret, perm, perm_stride, \
-                           start, count, params, param_stride, hyper, scratch, partial_stride);
-        PCC_MFMA_OBS_LENGTHS(PCC_PPO_CASE)
-#undef PCC_PPO_CASE
-    } else {
-        const pcc_tiles::GradPopArgs a{{obs, act, logp_old, adv, ret, perm, start, count, obs_dim, h1, h2, params, 0.0f, scratch},
-                                       perm_stride, param_stride, partial_stride, hyper, n_members};
-        int nb = 0;
-        const int rc = pcc_tiles::launch_grad_pop(a, st, &nb);
-        if (rc != 0) return rc;
-        blocks = nb;
-    }
-    if (hipGetLastError() != hipSuccess) return -3;
-    const float bias1 = 1.0f - powf(beta1, (float)adam_step);
-    const float bias2 = sqrtf(1.0f - powf(beta2, (float)adam_step));
-    hipLaunchKernelGGL(ppo_adam_pop_kernel, dim3((unsigned)((L.n_params() + 4 + 15) / 16), (unsigned)n_members), dim3(256), 0, st, scratch,
-                       partial_stride, (int)blocks, L.n_params(), L.log_std(), hyper, params, adam_m, adam_v, param_stride, beta1, beta2,
-                       eps, bias1, bias2, 1.0f / (float)count, grad_out, stats_out);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    if (param_stride < PolicyLayout(obs_dim, h1, h2).n_params() || param_stride % 64 != 0) return -1;
+    const pcc_tiles::GradArgs a{obs, act, logp_old, adv, ret, perm, perm_stride, start, count, obs_dim, h1, h2, params, param_stride,
+                                hyper, 0.0f, scratch, 0, n_members};
+    return launch_step(a, params, adam_m, adam_v, adam_step, 0.0f, beta1, beta2, eps, 0.0f, grad_out, stats_out,
+                       static_cast<hipStream_t>(stream));
 }
 
 extern "C" int pcc_gae_pop(const float *rewards, const float *values, const uint8_t *dones, const float *last_value, int T,
                            int64_t n_envs, int n_members, const float *hyper, float *adv_out, float *ret_out, void *stream) {
     if (!rewards || !values || !dones || !last_value || !hyper || !adv_out || !ret_out || T < 1 || n_envs < 1) return -1;
     if (n_members < 1 || n_members > 1024 || n_envs % n_members != 0) return -1;
-    const int64_t n_member = n_envs / n_members;
-    hipLaunchKernelGGL(gae_pop_kernel, dim3((unsigned)((n_member + 255) / 256), (unsigned)n_members), dim3(256),
-                       0, static_cast<hipStream_t>(stream), rewards, values, dones, last_value, T, n_envs, n_member, hyper, adv_out,
-                       ret_out);
-    return hipGetLastError() == hipSuccess ? 0 : -3;
+    return launch_gae(rewards, values, dones, last_value, T, n_envs, n_members, hyper, 0.0f, 0.0f, adv_out, ret_out, stream);
 }

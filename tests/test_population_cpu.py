@@ -1,5 +1,5 @@
 """Population PPO, the part that needs no GPU: the three C-ABI symbols (include/pcc_policy.h: pcc_policy_act_pop,
-pcc_ppo_minibatch_step_pop, pcc_gae_pop), the compiler's resource report of the population kernels, the sample-index helper and
+pcc_ppo_minibatch_step_pop, pcc_gae_pop), the compiler's resource report of the kernels they share with the stand-alone calls, the sample-index helper and
 the permutations, the per-member advantage normalisation, and what PopulationPPO's constructor refuses."""
 import json
 
@@ -25,29 +25,27 @@ def test_the_three_symbols_are_exported():
 
 
 def test_population_kernels_use_no_scratch(tmp_path):
-    """A build into a temporary file: every population kernel is in the compiler's resource report with 0 bytes of scratch and 0
-    spilled vector registers; the stand-alone kernels' lines are what tests/test_ppo_shapes.py pins."""
+    """A build into a temporary file: every PPO-stage kernel -- one per stage, its grid with a member dimension, serving the
+    stand-alone and the population entry points alike -- is in the compiler's resource report with 0 bytes of scratch and 0 spilled
+    vector registers, at the figures tests/test_ppo_shapes.py pins; no population twin and no copied body is left."""
     from pcc_rl_amd import build as pbuild
     out = str(tmp_path / "libpcc_sim_pop.so")
     pbuild.build_library(force=True, out=out)
     res = json.load(open(out + ".resources.json"))
-    names = ["ppo_adam_pop_kernel", "gae_pop_kernel"]
-    names += ["policy_act_fixed_pop_kernel<%d, 32, 16>" % D for D in FIXED] + ["policy_act_pop_kernel<%d>" % D for D in FIXED]
-    names += ["ppo_grad_mfma_pop_kernel<%d, 32, 16>" % D for D in MFMA]
-    for kern in ("ppo_grad_tiled_pop_kernel", "policy_act_tiled_pop_kernel"):
+    names = ["ppo_adam_kernel", "gae_kernel"]
+    names += ["policy_act_fixed_kernel<%d, 32, 16>" % D for D in FIXED] + ["policy_act_kernel<%d>" % D for D in FIXED]
+    names += ["ppo_grad_mfma_kernel<%d, 32, 16>" % D for D in MFMA]
+    for kern in ("ppo_grad_tiled_kernel", "policy_act_tiled_kernel"):
         names += ["pcc_tiles::%s<%d, %d, %d>" % (kern, D, h1, h2) for D in (32, 64, 128) for h1, h2 in ((32, 32), (64, 32), (64, 64))]
     for name in names:
         assert name in res, name
         assert res[name]["scratch"] == 0 and res[name]["vgpr_spills"] == 0, (name, res[name])
         assert res[name]["lds"] <= 160 * 1024, (name, res[name])
-    assert sorted(n for n in res if "_pop_kernel" in n) == sorted(names)   # no population kernel goes unchecked
-    for name in ("ppo_grad_mfma_kernel<30, 32, 16>", "policy_act_fixed_kernel<30, 32, 16>"):
-        assert res[name]["scratch"] == 0 and res[name]["vgpr_spills"] == 0, (name, res[name])
+    assert not [n for n in res if "_pop_kernel" in n or "_body" in n]
+    stages = ("ppo_adam", "gae_", "policy_act", "ppo_grad")   # no PPO-stage kernel goes unchecked
+    assert sorted(n for n in res if any(s in n for s in stages)) == sorted(names)
     assert (res["ppo_grad_mfma_kernel<30, 32, 16>"]["vgprs"], res["ppo_grad_mfma_kernel<30, 32, 16>"]["lds"]) == (256, 52736)
     assert res["policy_act_fixed_kernel<30, 32, 16>"]["vgprs"] == 87
-    # a population kernel of the two pinned shapes takes what its stand-alone kernel takes
-    assert (res["ppo_grad_mfma_pop_kernel<30, 32, 16>"]["vgprs"], res["ppo_grad_mfma_pop_kernel<30, 32, 16>"]["lds"]) == (256, 52736)
-    assert res["policy_act_fixed_pop_kernel<30, 32, 16>"]["vgprs"] == 87
 
 
 def test_sample_index_and_permutations():

@@ -144,6 +144,37 @@ def test_gradient_matches_float64_autograd(shape, n, count, with_perm):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("shape", [(30, 32, 16), (7, 20, 10)], ids=_ids)   # an MFMA shape; a tiled one whose forward is the generic kernel
+def test_null_perm_and_null_moments_equal_their_explicit_forms(shape):
+    """The two argument forms only the stand-alone entry point sends through the kernels it shares with the population's:
+    perm = NULL is perm = arange, and lr = 0 with NULL moments is lr = 0 with moments -- the same bits, params untouched."""
+    dev = torch.device("cuda:0")
+    D, h1, h2 = shape
+    n, start, count = 777, 1, 700
+    n_params = 2 * _n_net(D, h1, h2) + 1
+    obs, act, logp, adv, ret = _rollout_like(n, D, dev, 17)
+    params = (0.2 * torch.randn(n_params, generator=torch.Generator().manual_seed(3))).to(dev)
+    before = params.clone()
+    scratch = torch.empty(lib().pcc_ppo_scratch_floats(D, h1, h2), device=dev)
+    st = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def call(perm, m, v):
+        g, stats = torch.full((n_params,), float("nan"), device=dev), torch.full((4,), float("nan"), device=dev)
+        rc = lib().pcc_ppo_minibatch_step(_p(obs), _p(act.reshape(n)), _p(logp), _p(adv), _p(ret), _p(perm), start, count, D, h1, h2,
+                                          _p(params), _p(m), _p(v), 1, 0.0, 0.9, 0.999, 1e-5, 0.2, 0.01, _p(scratch), _p(g), _p(stats), st)
+        torch.cuda.synchronize()
+        return rc, g, stats
+    rc1, g1, s1 = call(None, None, None)
+    m, v = torch.zeros(n_params, device=dev), torch.zeros(n_params, device=dev)
+    rc2, g2, s2 = call(torch.arange(n, device=dev), m, v)
+    assert rc1 == 0 and rc2 == 0
+    assert torch.equal(g1, g2) and torch.equal(s1, s2)
+    assert torch.isfinite(g1).all() and g1.abs().max() > 0
+    assert torch.equal(params, before)
+    assert not m.any() and not v.any()                        # lr = 0: the moments are not touched either
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("n,count", [(5000, 3333), (70000, 70000)])   # (70 000: more tiles than the capped grid takes at once)
 @pytest.mark.parametrize("shape", SHAPES, ids=_ids)
 def test_gradient_is_deterministic(shape, n, count):

@@ -20,7 +20,7 @@ ap.add_argument("--horizon", type=int, default=64)
 ap.add_argument("--repeats", type=int, default=3)
 ap.add_argument("--inner", type=int, default=8, help="collect() calls, then update() calls, per timed window (an iteration is tens of milliseconds)")
 ap.add_argument("--trace-run", type=int, default=0, help="K: run variant (a) alone for two iterations and write nothing (for rocprofv3)")
-ap.add_argument("--merge-kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of a --trace-run: its population kernels go into --out")
+ap.add_argument("--merge-kernel-stats", default="", help="a rocprofv3 kernel_stats.csv of a --trace-run: its PPO-stage kernels go into --out")
 args = ap.parse_args()
 
 if args.merge_kernel_stats:
@@ -30,7 +30,7 @@ if args.merge_kernel_stats:
     with open(args.merge_kernel_stats) as f:
         for r in csv.DictReader(f):
             name = r.get("Name", "")
-            if "_pop_kernel" in name or any(k in name for k in ("policy_act_fixed_kernel", "ppo_grad_mfma_kernel", "ppo_adam_kernel", "gae_kernel")):
+            if any(k in name for k in ("policy_act_", "ppo_grad_", "ppo_adam_kernel", "gae_kernel")):   # the PPO-stage kernels (both entry points')
                 rows.append({"kernel": name.replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0], "calls": int(r["Calls"]),
                              "total_us": float(r["TotalDurationNs"]) / 1e3, "mean_us": float(r["AverageNs"]) / 1e3,
                              "share_of_gpu_time_pct": float(r["Percentage"])})

@@ -70,10 +70,12 @@ def main():
     ap.add_argument("--eval-envs", type=int, default=4096)
     ap.add_argument("--horizon", type=int, default=400)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--normalize-obs", action="store_true",
+                    help="train with PPO(normalize_obs=True); the held-out evaluation applies the trained, frozen normaliser")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device=dev, seed=args.seed)
-    agent = PPO(env, horizon=args.horizon, seed=args.seed)
+    agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs)
     untrained = {k: v.clone() for k, v in agent.policy.state_dict().items()}
     iters = max(1, int(round(args.env_steps / (args.envs * args.horizon))))
     curve = []
@@ -92,6 +94,8 @@ def main():
 
     def policy_mean(obs, env_, t, last):
         with torch.no_grad():
+            if args.normalize_obs:   # the trained normaliser, frozen: for the untrained network too (its inputs' scale is part of the set-up)
+                obs = agent.obs_norm.normalise(obs.contiguous())
             return pol.pi(obs).reshape(-1)
 
     results = [evaluate("trained", policy_mean, **held)]
@@ -116,6 +120,7 @@ def main():
     by = {r["controller"]: r for r in results}
     out = {"what": "PPO (reference hyper-parameters, pi/vf MLP 32-16) on the MI355X simulator, then the trained controller against "
                    "baselines on held-out envs; python examples/learning_curve.py",
+           "normalize_obs": bool(args.normalize_obs),
            "training": {"envs": args.envs, "horizon": args.horizon, "iterations": iters, "env_steps": iters * args.envs * args.horizon,
                         "reference_budget_env_steps": 6 * 1600 * 410, "wall_s": train_s,
                         "env_steps_per_s_incl_learning": iters * args.envs * args.horizon / train_s,

@@ -44,6 +44,11 @@ def main():
     ap.add_argument("--gammas", default="")
     ap.add_argument("--seeds", default="", help="one per member (default 0, 1, ...)")
     ap.add_argument("--save", default="", help="write every member's policy state_dict here (a list) at the end")
+    ap.add_argument("--normalize-obs", action="store_true",
+                    help="every member standardises its observations with its own running moments on the device "
+                    "(PopulationPPO(normalize_obs=True)); the normalisers travel in --checkpoint / --resume, --save and --export, and "
+                    "with the weights in a --pbt-every generation")
+    ap.add_argument("--export", default="", help="write every member's policy as TorchScript into <dir>/member<m> (export.export_policy)")
     ap.add_argument("--checkpoint", default="", help="write the whole training state here every --checkpoint-every iterations and at the end")
     ap.add_argument("--checkpoint-every", type=int, default=10)
     ap.add_argument("--resume", default="", help="continue from a --checkpoint file of a run with the same --members, --envs, --horizon and --arch")
@@ -60,7 +65,7 @@ def main():
     pop = PopulationPPO(env, args.members, arch=tuple(int(x) for x in args.arch.split(",")), horizon=args.horizon,
                         lr=values(args.lrs, 1e-3), ent_coef=values(args.ent_coefs, 0.01),
                         gamma=values(args.gammas, 0.99),
-                        seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None)
+                        seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None, normalize_obs=args.normalize_obs)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)
@@ -100,8 +105,14 @@ def main():
         curve["hyper_at_end"] = pop.hypers()
         with open(args.curve, "w") as f:
             json.dump(curve, f, indent=1)
+    norms = [pop.obs_norm.member(m) for m in range(args.members)] if args.normalize_obs else None   # (shift, scale, clip) per member
     if args.save:
-        torch.save([p.state_dict() for p in pop.policies], args.save)
+        states = [p.state_dict() for p in pop.policies]
+        torch.save({"policies": states, "obs_norm": norms} if args.normalize_obs else states, args.save)
+    if args.export:
+        from pcc_rl_amd.export import export_policy
+        for m, p in enumerate(pop.policies):
+            export_policy(p, os.path.join(args.export, "member%d" % m), obs_norm=norms[m] if norms else None)
 
 
 if __name__ == "__main__":

@@ -27,6 +27,10 @@ def main():
     ap.add_argument("--arch", default="32,16")
     ap.add_argument("--gamma", type=float, default=0.99)
     ap.add_argument("--save", default="")
+    ap.add_argument("--normalize-obs", action="store_true",
+                    help="standardise the observations with running moments on the device (PPO(normalize_obs=True)); the normaliser "
+                    "travels in --checkpoint / --resume, in --save and in --export")
+    ap.add_argument("--export", default="", help="write the trained policy here as TorchScript (export.export_policy)")
     ap.add_argument("--policy-in-step", action="store_true",
                     help="collect each horizon as one closed-loop call (pcc_rollout): the policy inside the env's launches")
     ap.add_argument("--checkpoint", default="", help="write the whole training state here (PPO.state_dict: policy, Adam, generators, "
@@ -39,7 +43,7 @@ def main():
     pools = tuple(int(x) for x in args.ring_pools.split(",")) if args.ring_pools else ((2, 8, 32) if args.checkpoint or args.resume else None)
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0, ring_pools=pools)
     agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
-                policy_in_step=args.policy_in_step)
+                policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)
@@ -59,8 +63,12 @@ def main():
         steps = (it + 1 - first) * args.envs * args.horizon
         print("iter %3d  env-steps %10d  reward/step %8.4f  entropy %6.3f  %.0f env-steps/s incl. learning"
               % (it, steps, s["mean_step_reward"], s["entropy"], steps / (time.perf_counter() - t0)))
+    obs_norm = agent.obs_norm.member(0) if args.normalize_obs else None   # (shift, scale, clip): the policy is meaningless without it
     if args.save:
-        torch.save(agent.policy.state_dict(), args.save)
+        torch.save({"policy": agent.policy.state_dict(), "obs_norm": obs_norm} if args.normalize_obs else agent.policy.state_dict(), args.save)
+    if args.export:
+        from pcc_rl_amd.export import export_policy
+        export_policy(agent.policy, args.export, obs_norm=obs_norm)
 
 
 if __name__ == "__main__":

@@ -129,6 +129,43 @@ int pcc_pbt_evolve(const double *score, int n_members, int n_cut, float *params,
                    int64_t param_stride, int64_t n_params, float *hyper, const float *explore, uint64_t seed,
                    uint32_t generation, int32_t *parent_out, int32_t *rank_out, void *stream);
 
+/*
+ * Observation normalisation: running per-member, per-feature moments of the raw observation rows, and
+ * the standardised, clipped rows the policy kernels read.  All buffers are caller-owned device memory; everything is enqueued
+ * on `stream`, nothing synchronizes.  Member m owns the columns [m * n_envs / n_members, (m + 1) * n_envs / n_members) of every
+ * [.][n_envs][obs_dim] row block, as above.
+ * stats     float64 [n_members][stat_stride], stat_stride >= 1 + 2 * obs_dim: row m is {count, mean[obs_dim], m2[obs_dim]}, m2 the
+ *           sum of squared deviations; the padding is never read or written; all zeros is the empty state
+ * norm      float32 [n_members][2 * obs_dim]: row m is {shift[obs_dim], scale[obs_dim]}
+ *
+ * pcc_obs_stats_update_pop, two launches: for every member the moments (n_b = T * n_envs / n_members, mean_b, m2_b) of its rows of
+ * obs[T][n_envs][obs_dim], accumulated in float64 (partial moments per workgroup into scratch, then one workgroup per member
+ * combines them in a fixed order), merged into row m of stats by Chan's formula -- n = n_a + n_b, d = mean_b - mean_a,
+ * mean = mean_a + d * n_b / n, m2 = m2_a + m2_b + d * d * n_a * n_b / n; a row with count == 0 becomes the batch's moments -- and,
+ * if norm != NULL, shift[d] = (float)mean[d], scale[d] = (float)(1.0 / sqrt(m2[d] / count + eps)): IEEE float64 arithmetic,
+ * rounded to float32 once.  scratch is pcc_obs_stats_scratch_doubles(T, n_envs, obs_dim, n_members) doubles (host only; -1
+ * outside the domain).
+ *
+ * pcc_obs_normalise_pop, one launch, one [n_envs][obs_dim] row block: out = fminf(fmaxf((x - shift[d]) * scale[d], -clip), clip),
+ * three float32 operations, no contraction.  out == obs is allowed.
+ *
+ * No atomics, no hand-off between workgroups: the same inputs give the same bits, and a member's stats, norm and out are
+ * bit-identical to the stand-alone call on a contiguous copy of its columns (a member is cut into workgroups exactly as a launch
+ * over the member alone; no divisibility is asked of the member size).  pcc_obs_stats_update / pcc_obs_normalise are the
+ * stand-alone forms: the same kernels with one member and stat_stride = 1 + 2 * obs_dim.
+ * Returns 0; -1, with nothing written and before any device call, outside 1 <= obs_dim <= 128, 1 <= n_members <= 1024,
+ * n_envs % n_members == 0, T >= 1, clip > 0, eps >= 0, stat_stride >= 1 + 2 * obs_dim, or for a NULL obs / stats / scratch / out
+ * (pcc_obs_normalise_pop: a NULL norm too); -3 launch failure.
+ */
+int pcc_obs_stats_scratch_doubles(int T, int64_t n_envs, int obs_dim, int n_members);
+int pcc_obs_stats_update_pop(const float *obs, int T, int64_t n_envs, int obs_dim, int n_members, double *stats,
+                             int64_t stat_stride, float *norm, double eps, double *scratch, void *stream);
+int pcc_obs_normalise_pop(const float *obs, int64_t n_envs, int obs_dim, int n_members, const float *norm, float clip,
+                          float *out, void *stream);
+int pcc_obs_stats_update(const float *obs, int T, int64_t n_envs, int obs_dim, double *stats, float *norm, double eps,
+                         double *scratch, void *stream);
+int pcc_obs_normalise(const float *obs, int64_t n_envs, int obs_dim, const float *norm, float clip, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,19 +25,46 @@ class _Exported(nn.Module):
         return act, stochastic_act
 
 
-def export_policy(policy, export_dir, history_len=10, features=None):
-    """Write <export_dir>/policy.pt (TorchScript, CPU) and signature.json naming inputs and outputs."""
+class _ExportedNormalised(nn.Module):
+    """_Exported behind the trained, frozen observation normaliser (obsnorm.ObsNormalizer.member): the module takes raw
+    observations, like the one of a policy trained without normalisation."""
+
+    def __init__(self, pi, log_std, shift, scale, clip: float):
+        super().__init__()
+        self.pi = pi
+        self.log_std = nn.Parameter(log_std.detach().clone(), requires_grad=False)
+        self.register_buffer("shift", shift.detach().clone().float().reshape(-1))
+        self.register_buffer("scale", scale.detach().clone().float().reshape(-1))
+        self.clip = float(clip)
+
+    def forward(self, ob: torch.Tensor):
+        act = self.pi(torch.clamp((ob - self.shift) * self.scale, -self.clip, self.clip))
+        stochastic_act = act + torch.randn_like(act) * torch.exp(self.log_std)
+        return act, stochastic_act
+
+
+def export_policy(policy, export_dir, history_len=10, features=None, obs_norm=None):
+    """Write <export_dir>/policy.pt (TorchScript, CPU) and signature.json naming inputs and outputs.
+    obs_norm: (shift, scale, clip) of a policy trained with normalize_obs (ObsNormalizer.member(m)): the module applies
+    clamp((ob - shift) * scale, -clip, clip) before pi, and signature.json says "obs_norm": true."""
     os.makedirs(export_dir, exist_ok=True)
     # a COPY of the network goes to the CPU: nn.Module.to() moves parameters in place, and the caller's policy (and its
     # optimizer state) must stay where it is
-    mod = _Exported(copy.deepcopy(policy.pi), policy.log_std).to("cpu").eval()
+    if obs_norm is None:
+        mod = _Exported(copy.deepcopy(policy.pi), policy.log_std).to("cpu").eval()
+    else:
+        shift, scale, clip = obs_norm
+        mod = _ExportedNormalised(copy.deepcopy(policy.pi), policy.log_std, shift.cpu(), scale.cpu(), clip).to("cpu").eval()
     scripted = torch.jit.script(mod)
     path = os.path.join(export_dir, "policy.pt")
     scripted.save(path)
     obs_dim = policy.pi[0].in_features
+    sig = {"inputs": {"ob": [None, obs_dim]}, "outputs": {"act": [None, 1], "stochastic_act": [None, 1]},
+           "history_len": history_len, "features": features, "format": "torchscript"}
+    if obs_norm is not None:
+        sig["obs_norm"] = True
     with open(os.path.join(export_dir, "signature.json"), "w") as f:
-        json.dump({"inputs": {"ob": [None, obs_dim]}, "outputs": {"act": [None, 1], "stochastic_act": [None, 1]},
-                   "history_len": history_len, "features": features, "format": "torchscript"}, f, indent=1)
+        json.dump(sig, f, indent=1)
     return path
 
 

@@ -200,18 +200,41 @@ def ppo_loss(policy, obs, act, logp_old, adv, ret, clip=0.2, ent_coef=0.01):
     return pg + vf - ent_coef * ent, pg, vf, ent
 
 
+def _refuse_normalize(normalize_obs, policy_in_step, env):
+    """normalize_obs needs the rows between the env and the policy: not with the policy inside the env's launches."""
+    if not normalize_obs:
+        return
+    if policy_in_step:
+        raise ValueError("normalize_obs=True cannot be combined with policy_in_step=True: the policy inside the env's launches "
+                         "(pcc_rollout) reads the raw observation rows, not the normalised ones")
+    if hasattr(env, "groups"):
+        raise ValueError("normalize_obs=True is not supported over a GroupedNetworkEnv: its groups are stepped on their own streams "
+                         "and the policy reads the raw observation rows there")
+
+
+def _check_normalize(sd, normalize_obs):
+    if bool(sd.get("normalize_obs", False)) != bool(normalize_obs):
+        raise ValueError("the checkpoint was written with normalize_obs=%s, this object has normalize_obs=%s: weights without "
+                         "their normaliser are meaningless" % (bool(sd.get("normalize_obs", False)), bool(normalize_obs)))
+
+
 class PPO(object):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
-                 epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False):
+                 epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
+                 normalize_obs=False, clip_obs=10.0, norm_eps=1e-8):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
         optimiser steps per epoch, thousands of launches of a few microseconds of work each.
         policy_in_step: collect() runs the horizon as ONE closed-loop library call per env (group) -- env.rollout, pcc_rollout:
-        the policy inside the env's own launches -- with the same numbers, bit for bit, as the policy kernel + step_into loop."""
+        the policy inside the env's own launches -- with the same numbers, bit for bit, as the policy kernel + step_into loop.
+        normalize_obs: the policy sees clamp((obs - mean) / sqrt(var + norm_eps), -clip_obs, clip_obs) with the running moments of
+        the raw rows (obsnorm.ObsNormalizer): frozen during a rollout, updated once at its end."""
         if policy_in_step and torch.device(env.device).type != "cuda":
             raise ValueError("PPO(policy_in_step=True) runs the policy inside the env's HIP launches: it needs the env on the GPU "
                              "(device=%r)" % (env.device,))
         self.policy_in_step = bool(policy_in_step)
+        self.normalize_obs = bool(normalize_obs)
+        _refuse_normalize(self.normalize_obs, policy_in_step, env)
         self.env, self.gamma, self.lam, self.clip, self.ent_coef = env, gamma, lam, clip, ent_coef
         self.epochs, self.minibatch, self.horizon = epochs, minibatch, horizon
         torch.manual_seed(seed)
@@ -236,6 +259,11 @@ class PPO(object):
             self.stats_buf = torch.zeros(4, device=env.device)
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=lr, eps=self.adam_eps)
         self.obs = env.reset().clone()
+        if self.normalize_obs:
+            from .obsnorm import ObsNormalizer
+            self.obs_norm = ObsNormalizer(env.obs_dim, 1, clip_obs, norm_eps, device=env.device)
+            self.raw_obs = self.obs
+            self.obs = self.obs_norm.normalise(self.raw_obs)
         if self.minibatch is None:
             self.minibatch = max(2048, env.n_envs * horizon // 4)
 
@@ -259,7 +287,15 @@ class PPO(object):
         val_b = torch.empty((T, N), device=dev)
         rew_b = torch.empty((T, N), device=dev)
         done_b = torch.empty((T, N), dtype=torch.bool, device=dev)
-        obs_b[0] = self.obs
+        if self.normalize_obs:
+            # the env writes raw rows; after each step ONE normalise launch fills the row the policy reads.  The statistics are
+            # frozen during the rollout: logp_old, the values and the update all see the same inputs.
+            norm = self.obs_norm
+            raw_b = torch.empty((T + 1, N, env.obs_dim), device=dev)
+            raw_b[0] = self.raw_obs
+            norm.normalise(raw_b[0], obs_b[0])
+        else:
+            obs_b[0] = self.obs
         fused = self.policy.fused_ok(obs_b[0]) and env.n_senders == 1
         groups = getattr(env, "groups", None)
         if self.policy_in_step and not fused:
@@ -320,15 +356,27 @@ class PPO(object):
             noise = torch.randn((T, N), device=dev)                # the horizon's draws in one launch
             for t in range(T):
                 self.policy.act_fused(obs_b[t], True, params, noise[t], (act_b[t].reshape(N), logp_b[t], val_b[t]))
-                env.step_into(act_b[t], obs_b[t + 1], rew_b[t], done_b[t])   # tensors in, tensors out, no host round trip
+                if self.normalize_obs:
+                    env.step_into(act_b[t], raw_b[t + 1], rew_b[t], done_b[t])
+                    norm.normalise(raw_b[t + 1], obs_b[t + 1])
+                else:
+                    env.step_into(act_b[t], obs_b[t + 1], rew_b[t], done_b[t])   # tensors in, tensors out, no host round trip
         else:
             for t in range(T):
                 a, logp, v = self.policy.act(obs_b[t])
                 act_b[t], logp_b[t], val_b[t] = a, logp, v
                 nobs, r, d, _ = env.step(a)
-                rew_b[t], done_b[t], obs_b[t + 1] = r, d, nobs
+                if self.normalize_obs:
+                    raw_b[t + 1] = nobs
+                    norm.normalise(raw_b[t + 1], obs_b[t + 1])
+                else:
+                    obs_b[t + 1] = nobs
+                rew_b[t], done_b[t] = r, d
         obs = obs_b[T]
         self.obs = obs.clone()
+        if self.normalize_obs:
+            self.raw_b, self.raw_obs = raw_b, raw_b[T].clone()
+            norm.update(raw_b[:T])   # rows 0 .. T - 1: what the policy saw
         obs_b = obs_b[:T]
         with torch.no_grad():
             last_v = self.policy.value(obs)
@@ -403,6 +451,8 @@ class PPO(object):
             sd.update(flat=self.flat.detach().clone(), adam_m=self.adam_m.clone(), adam_v=self.adam_v.clone(), adam_t=int(self.adam_t))
         else:
             sd.update(policy={k: v.detach().clone() for k, v in self.policy.state_dict().items()}, opt=self.opt.state_dict())
+        if self.normalize_obs:   # (without it the keys are what they were)
+            sd.update(normalize_obs=True, obs_norm=self.obs_norm.state_dict(), raw_obs=self.raw_obs.detach().clone())
         return sd
 
     def load_state_dict(self, sd):
@@ -415,6 +465,7 @@ class PPO(object):
         if bool(sd["fused_update"]) != self.fused_update or sd["obs_dim"] != int(self.env.obs_dim) or sd["n_envs"] != int(self.env.n_envs):
             raise ValueError("the checkpoint is of another PPO: fused_update=%s, obs_dim=%d, n_envs=%d; this one: %s, %d, %d"
                              % (sd["fused_update"], sd["obs_dim"], sd["n_envs"], self.fused_update, self.env.obs_dim, self.env.n_envs))
+        _check_normalize(sd, self.normalize_obs)
         if self.fused_update and sd["flat"].numel() != self.flat.numel():
             raise ValueError("the checkpoint's policy has %d parameters, this one %d (another --arch)" % (sd["flat"].numel(), self.flat.numel()))
         self.env.restore(sd["env"])
@@ -428,6 +479,9 @@ class PPO(object):
             self.policy.load_state_dict(sd["policy"])
             self.opt.load_state_dict(sd["opt"])
         self.obs = sd["obs"].to(dev).clone()
+        if self.normalize_obs:
+            self.obs_norm.load_state_dict(sd["obs_norm"])
+            self.raw_obs = sd["raw_obs"].to(dev).clone()
         torch.set_rng_state(sd["torch_rng"].cpu())
         if dev.type == "cuda" and sd.get("device_rng") is not None:
             torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)
@@ -502,10 +556,12 @@ class PopulationPPO(object):
     for raises ValueError."""
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
-                 epochs=4, minibatch=None, horizon=64):
+                 epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8):
         from .env import BatchedNetworkEnv
         from .native import lib
         members = int(members)
+        self.normalize_obs = bool(normalize_obs)
+        _refuse_normalize(self.normalize_obs, False, env)
         if members < 1 or members > 1024:
             raise ValueError("PopulationPPO: members = %d (1 .. 1024)" % members)
         if len(arch) != 2:
@@ -551,6 +607,11 @@ class PopulationPPO(object):
         self.scratch = torch.empty(members * self.scratch_floats, device=dev)
         self.stats_buf = torch.zeros((members, 4), device=dev)
         self.obs = env.reset().clone()
+        if self.normalize_obs:   # every member its own moments of its own columns (obsnorm.ObsNormalizer)
+            from .obsnorm import ObsNormalizer
+            self.obs_norm = ObsNormalizer(D, members, clip_obs, norm_eps, device=dev)
+            self.raw_obs = self.obs
+            self.obs = self.obs_norm.normalise(self.raw_obs)
         per_member = self.n_member * horizon
         self.minibatch = min(per_member, max(2048, per_member // 4)) if minibatch is None else int(minibatch)
 
@@ -588,18 +649,32 @@ class PopulationPPO(object):
         act_b = torch.empty((T, N, 1), device=dev)
         logp_b, val_b, rew_b = (torch.empty((T, N), device=dev) for _ in range(3))
         done_b = torch.empty((T, N), dtype=torch.bool, device=dev)
-        obs_b[0] = self.obs
+        if self.normalize_obs:   # as PPO.collect: raw rows from the env, one normalise launch per step, frozen statistics
+            norm = self.obs_norm
+            raw_b = torch.empty((T + 1, N, env.obs_dim), device=dev)
+            raw_b[0] = self.raw_obs
+            norm.normalise(raw_b[0], obs_b[0])
+        else:
+            obs_b[0] = self.obs
         if noise is None:
             noise = torch.randn((T, N), device=dev)
         for t in range(T):
             self._act(obs_b[t], noise[t], act_b[t].reshape(N), logp_b[t], val_b[t])
-            env.step_into(act_b[t], obs_b[t + 1], rew_b[t], done_b[t])
+            if self.normalize_obs:
+                env.step_into(act_b[t], raw_b[t + 1], rew_b[t], done_b[t])
+                norm.normalise(raw_b[t + 1], obs_b[t + 1])
+            else:
+                env.step_into(act_b[t], obs_b[t + 1], rew_b[t], done_b[t])
         self.obs = obs_b[T].clone()
+        if self.normalize_obs:
+            self.raw_b, self.raw_obs = raw_b, raw_b[T].clone()
         last_v = torch.empty(N, device=dev)
         self._act(obs_b[T], None, None, None, last_v)
         env.check_flags()
         adv, ret = self._gae(rew_b, val_b, done_b, last_v)
         self.val_b, self.done_b = val_b, done_b
+        if self.normalize_obs:
+            norm.update(raw_b[:T])   # rows 0 .. T - 1: what the policies saw
         return obs_b[:T], act_b, logp_b, adv, ret, rew_b
 
     def normalise(self, adv):
@@ -668,6 +743,8 @@ class PopulationPPO(object):
                                   self.generation & 0xFFFFFFFF, _ptr(parent), _ptr(rank), self._stream())
         if rc != 0:
             raise RuntimeError("pcc_pbt_evolve failed (%d)" % rc)
+        if self.normalize_obs:   # weights without their normaliser are meaningless: a replaced member takes its parent's too
+            self.obs_norm.inherit(parent)
         self.generation += 1
         self.hyper_rows = None
         return parent, rank
@@ -680,10 +757,13 @@ class PopulationPPO(object):
         """Everything the next iterate() depends on (PPO.state_dict's contract): the flat block, Adam's state and step, hyper, the
         observation, the generator states and the env's snapshot; and the generation the next evolve() draws with."""
         dev = torch.device(self.env.device)
-        return {"format": "population-1", "members": self.members, "obs_dim": int(self.env.obs_dim), "n_envs": int(self.env.n_envs),
-                "arch": self.arch, "flat": self.flat.detach().clone(), "adam_m": self.adam_m.clone(), "adam_v": self.adam_v.clone(),
-                "adam_t": int(self.adam_t), "generation": int(self.generation), "hyper": self.hyper.clone(), "obs": self.obs.detach().clone(),
-                "torch_rng": torch.get_rng_state(), "device_rng": torch.cuda.get_rng_state(dev), "env": self.env.snapshot()}
+        sd = {"format": "population-1", "members": self.members, "obs_dim": int(self.env.obs_dim), "n_envs": int(self.env.n_envs),
+              "arch": self.arch, "flat": self.flat.detach().clone(), "adam_m": self.adam_m.clone(), "adam_v": self.adam_v.clone(),
+              "adam_t": int(self.adam_t), "generation": int(self.generation), "hyper": self.hyper.clone(), "obs": self.obs.detach().clone(),
+              "torch_rng": torch.get_rng_state(), "device_rng": torch.cuda.get_rng_state(dev), "env": self.env.snapshot()}
+        if self.normalize_obs:   # (without it the keys are what they were)
+            sd.update(normalize_obs=True, obs_norm=self.obs_norm.state_dict(), raw_obs=self.raw_obs.detach().clone())
+        return sd
 
     def load_state_dict(self, sd):
         """Continue from a state_dict() of a PopulationPPO of the same construction (env configuration, members, arch)."""
@@ -694,6 +774,7 @@ class PopulationPPO(object):
         theirs = (sd["members"], sd["obs_dim"], sd["n_envs"], tuple(sd["arch"]))
         if mine != theirs:
             raise ValueError("the checkpoint is of another population: (members, obs_dim, n_envs, arch) = %s; this one: %s" % (theirs, mine))
+        _check_normalize(sd, self.normalize_obs)
         self.env.restore(sd["env"])
         with torch.no_grad():
             self.flat.copy_(sd["flat"])       # (the policies' parameters are views of its rows)
@@ -704,5 +785,8 @@ class PopulationPPO(object):
         self.adam_t = int(sd["adam_t"])
         self.generation = int(sd.get("generation", 0))   # (a checkpoint from before evolve() has none)
         self.obs = sd["obs"].to(dev).clone()
+        if self.normalize_obs:
+            self.obs_norm.load_state_dict(sd["obs_norm"])
+            self.raw_obs = sd["raw_obs"].to(dev).clone()
         torch.set_rng_state(sd["torch_rng"].cpu())
         torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)

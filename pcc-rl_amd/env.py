@@ -197,7 +197,7 @@ class BatchedNetworkEnv(object):
 
     # ------------------------------------------------------------------ configuration
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return native.current_stream(self.device)
 
     def _as_param(self, x, per_sender=False):
         shape = (self.n_senders, self.n_envs) if per_sender else (self.n_envs,)
@@ -564,6 +564,7 @@ class GroupedNetworkEnv(object):
             with torch.cuda.stream(self.streams[g]):
                 self.groups.append(BatchedNetworkEnv(self.group_size, device=self.device, seed=seed,
                                                      env_gid_base=int(env_gid_base) + g * self.group_size, **kwargs))
+        self.obs_dim, self.n_senders = self.groups[0].obs_dim, self.groups[0].n_senders   # the surface of a BatchedNetworkEnv, from its groups
 
     def reset_group(self, g, mask=None):
         with torch.cuda.stream(self.streams[g]):

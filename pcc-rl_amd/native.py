@@ -5,6 +5,8 @@ binding's entry points raises, loudly, with the build command to run."""
 import ctypes
 import os
 
+import torch
+
 from .build import build_library, library_path
 
 PCC_RNG_PHILOX, PCC_RNG_TRACE = 0, 1
@@ -164,3 +166,15 @@ def lib():
 def check(code):
     if code != 0:
         raise PccError(code, lib().pcc_last_error().decode("utf-8", "replace"))
+
+
+def call(name, *args):
+    """lib().<name>(*args) for an entry point of include/pcc_policy.h that returns 0 or an error code: a code raises."""
+    rc = getattr(lib(), name)(*args)
+    if rc != 0:
+        raise RuntimeError("%s failed (%d)" % (name, rc))
+
+
+def current_stream(device):
+    """torch's current stream on `device`, as the `stream` argument of the C ABI."""
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)

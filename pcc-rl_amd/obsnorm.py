@@ -2,11 +2,10 @@
 section 19): running per-member, per-feature mean and variance of the raw observation rows in float64, and the standardised,
 clipped rows the policy kernels read -- stable-baselines' VecNormalize / baselines-ppo1's ob_rms, as one library call for all
 members of a population.  There is no framework path: the HIP library does the work or the call raises."""
-import ctypes
-
 import torch
 
 from .env import _ptr
+from .native import call, current_stream, lib
 
 
 class ObsNormalizer(object):
@@ -28,9 +27,6 @@ class ObsNormalizer(object):
         self.norm = torch.cat([torch.zeros((self.members, D)), torch.ones((self.members, D))], dim=1).to(self.device).contiguous()
         self._scratch = None
 
-    def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
     def _rows(self, x, dims):
         if not (x.is_cuda and x.dtype == torch.float32 and x.is_contiguous() and x.dim() == dims and x.shape[-1] == self.obs_dim):
             raise ValueError("ObsNormalizer: expected contiguous float32 rows of %d observations on the GPU, got %s %s"
@@ -42,18 +38,14 @@ class ObsNormalizer(object):
     def normalise(self, raw_rows, out=None):
         """out[N][D] = clamp((raw_rows - shift) * scale, -clip, clip) with every member's row of norm: one launch.  out may be
         raw_rows itself; default: a new tensor."""
-        from .native import lib
         raw_rows = self._rows(raw_rows, 2)
         out = torch.empty_like(raw_rows) if out is None else self._rows(out, 2)
         N, D = raw_rows.shape
-        rc = lib().pcc_obs_normalise_pop(_ptr(raw_rows), N, D, self.members, _ptr(self.norm), self.clip, _ptr(out), self._stream())
-        if rc != 0:
-            raise RuntimeError("pcc_obs_normalise_pop failed (%d)" % rc)
+        call("pcc_obs_normalise_pop", _ptr(raw_rows), N, D, self.members, _ptr(self.norm), self.clip, _ptr(out), current_stream(self.device))
         return out
 
     def update(self, raw_b):
         """Merge the moments of raw_b[T][N][D] into every member's statistics and rewrite norm: two launches."""
-        from .native import lib
         raw_b = self._rows(raw_b, 3)
         T, N, D = raw_b.shape
         need = lib().pcc_obs_stats_scratch_doubles(T, N, D, self.members)
@@ -61,10 +53,8 @@ class ObsNormalizer(object):
             raise ValueError("ObsNormalizer.update: a batch of %s is outside the library's domain" % (tuple(raw_b.shape),))
         if self._scratch is None or self._scratch.numel() < need:
             self._scratch = torch.empty(need, dtype=torch.float64, device=self.device)
-        rc = lib().pcc_obs_stats_update_pop(_ptr(raw_b), T, N, D, self.members, _ptr(self.stats), self.stat_stride, _ptr(self.norm),
-                                            self.eps, _ptr(self._scratch), self._stream())
-        if rc != 0:
-            raise RuntimeError("pcc_obs_stats_update_pop failed (%d)" % rc)
+        call("pcc_obs_stats_update_pop", _ptr(raw_b), T, N, D, self.members, _ptr(self.stats), self.stat_stride, _ptr(self.norm),
+             self.eps, _ptr(self._scratch), current_stream(self.device))
 
     def member(self, m):
         """(shift, scale, clip) of member m, the tensors on the CPU: what export.export_policy(obs_norm=...) takes.  A synchronise."""

@@ -16,14 +16,23 @@ fp32-MFMA gradient kernel and the Adam step (pcc_ppo.hip: pcc_ppo_minibatch_step
 --arch and observation lengths of the library's domain (pcc_ppo_supported: csrc/pcc_mlp_tiles.h); that a short run on the GPU improves
 the return; and what the whole loop costs next to the env alone (tools/ppo_throughput.py,
 profiles/r04_v2_ppo_throughput.json).
+
+Two trainers share this module.  PPO is the single policy: a rollout is one of four strategies
+(PPO._rollout_*: the policy inside the env's launches, the double-buffered loop over a GroupedNetworkEnv's groups, the fused
+loop, the framework loop), the update the fused step or autograd.  PopulationPPO is K learners on slices of one env batch, one
+library call per stage for all of them, and evolve() between generations.  What the two have in common is written once:
+_RolloutRows (the buffers of a rollout, the observation normaliser's place in it, and the fused loop), _Trainer (the first
+observation, the checkpoint's common part) and native.call / native.current_stream.  They stay two classes: PPO draws its
+permutations with randperm and takes the last value from the torch module, and a merge would change its numbers.
 """
-import ctypes
 import math
 
 import torch
 from torch import nn
 
-from .env import _ptr
+from .env import BatchedNetworkEnv, _ptr
+from .native import call, current_stream, lib
+from .obsnorm import ObsNormalizer
 
 
 class AlignedLinear(nn.Linear):
@@ -128,7 +137,6 @@ class MlpPolicy(nn.Module):
         """act() as ONE kernel launch of the HIP library; returns (action [N, 1], log-probability [N], value [N]) like act().
         A rollout loop passes `params` (flat_params(), built once per rollout -- it is a 13-tensor torch.cat), its own
         `noise` row and `out` = (action, logp, value) rows of its buffers, so that a step adds no framework launch."""
-        from .native import lib
         if not self.fused_ok(obs):
             _warn_once("the policy forward runs on the framework path (no pcc_policy_act for this policy / observation batch)")
             return self.act(obs, stochastic)
@@ -144,8 +152,7 @@ class MlpPolicy(nn.Module):
         else:
             a, logp, v = out
         rc = lib().pcc_policy_act(_ptr(obs.contiguous()), n, D, _ptr(params), h1, h2,
-                                  _ptr(noise if stochastic else None), None, _ptr(a), _ptr(logp), _ptr(v),
-                                  ctypes.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream))
+                                  _ptr(noise if stochastic else None), None, _ptr(a), _ptr(logp), _ptr(v), current_stream(obs.device))
         if rc != 0:   # a shape outside the library's domain (include/pcc_policy.h: pcc_ppo_supported)
             _warn_once("pcc_policy_act has no kernel for %d observations x hidden %d-%d: the policy forward runs on the framework "
                        "path (several times slower)" % (D, h1, h2))
@@ -174,17 +181,14 @@ def gae(rewards, values, dones, last_value, gamma=0.99, lam=0.95):
 
 def gae_fused(rewards, values, dones, last_value, gamma=0.99, lam=0.95):
     """gae() as one launch of the HIP library (pcc_gae: thread = env, T steps backwards) for fp32 [T, N] rows on the GPU."""
-    from .native import lib
     if not (rewards.is_cuda and rewards.dtype == torch.float32 and rewards.dim() == 2):
         return gae(rewards, values, dones, last_value, gamma, lam)
     T, N = rewards.shape
     rewards, values, last_value = rewards.contiguous(), values.contiguous(), last_value.contiguous().float()
     d8 = dones.contiguous().view(torch.uint8) if dones.dtype == torch.bool else dones.to(torch.uint8).contiguous()
     adv, ret = torch.empty_like(rewards), torch.empty_like(rewards)
-    rc = lib().pcc_gae(_ptr(rewards), _ptr(values), _ptr(d8), _ptr(last_value), T, N, gamma, lam, _ptr(adv), _ptr(ret),
-                       ctypes.c_void_p(torch.cuda.current_stream(rewards.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError("pcc_gae failed (%d)" % rc)
+    call("pcc_gae", _ptr(rewards), _ptr(values), _ptr(d8), _ptr(last_value), T, N, gamma, lam, _ptr(adv), _ptr(ret),
+         current_stream(rewards.device))
     return adv, ret
 
 
@@ -200,25 +204,118 @@ def ppo_loss(policy, obs, act, logp_old, adv, ret, clip=0.2, ent_coef=0.01):
     return pg + vf - ent_coef * ent, pg, vf, ent
 
 
-def _refuse_normalize(normalize_obs, policy_in_step, env):
-    """normalize_obs needs the rows between the env and the policy: not with the policy inside the env's launches."""
-    if not normalize_obs:
-        return
-    if policy_in_step:
-        raise ValueError("normalize_obs=True cannot be combined with policy_in_step=True: the policy inside the env's launches "
-                         "(pcc_rollout) reads the raw observation rows, not the normalised ones")
-    if hasattr(env, "groups"):
-        raise ValueError("normalize_obs=True is not supported over a GroupedNetworkEnv: its groups are stepped on their own streams "
-                         "and the policy reads the raw observation rows there")
+class _RolloutRows(object):
+    """The rows of one rollout of T steps of N envs, for both trainers: obs[T + 1] (row t: what the policy saw at step t; row T:
+    the last), act, logp, val, rew, done.  `dst` is what the env writes its observations into, row t + 1 for step t: obs itself,
+    or, with an observation normaliser, raw rows of its own -- after each step ONE normalise launch then fills the row the policy
+    reads.  The statistics are frozen during the rollout (logp_old, the values and the update all see the same inputs) and
+    updated once at its end."""
+
+    def __init__(self, agent, T, N):
+        dev, D = agent.env.device, agent.env.obs_dim
+        self.T, self.N = T, N
+        self.obs = torch.empty((T + 1, N, D), device=dev)
+        self.act = torch.empty((T, N, 1), device=dev)
+        self.logp, self.val, self.rew = (torch.empty((T, N), device=dev) for _ in range(3))
+        self.done = torch.empty((T, N), dtype=torch.bool, device=dev)
+        self.norm = agent.obs_norm if agent.normalize_obs else None
+        if self.norm is None:
+            self.dst = self.obs
+            self.obs[0] = agent.obs
+        else:
+            self.dst = torch.empty((T + 1, N, D), device=dev)
+            self.dst[0] = agent.raw_obs
+            self.norm.normalise(self.dst[0], self.obs[0])
+
+    def stepped(self, t):
+        """After the env wrote row t + 1 of dst."""
+        if self.norm is not None:
+            self.norm.normalise(self.dst[t + 1], self.obs[t + 1])
+
+    def run(self, env, noise, act):
+        """The fused loop: per step act(observation row, noise row, action, log-probability and value rows) -- one policy launch --
+        and the env's step from that action row into the next rows: tensors in, tensors out, no framework launch, no copy."""
+        for t in range(self.T):
+            act(self.obs[t], noise[t], self.act[t].reshape(self.N), self.logp[t], self.val[t])
+            env.step_into(self.act[t], self.dst[t + 1], self.rew[t], self.done[t])
+            self.stepped(t)
+
+    def finish(self, agent):
+        """The agent's observation for the next rollout and the normaliser's update from rows 0 .. T - 1 (what the policy saw);
+        returns the last observation row."""
+        T = self.T
+        agent.obs = self.obs[T].clone()
+        if self.norm is not None:
+            agent.raw_b, agent.raw_obs = self.dst, self.dst[T].clone()
+            self.norm.update(self.dst[:T])
+        return self.obs[T]
 
 
-def _check_normalize(sd, normalize_obs):
-    if bool(sd.get("normalize_obs", False)) != bool(normalize_obs):
-        raise ValueError("the checkpoint was written with normalize_obs=%s, this object has normalize_obs=%s: weights without "
-                         "their normaliser are meaningless" % (bool(sd.get("normalize_obs", False)), bool(normalize_obs)))
+class _Trainer(object):
+    """What PPO and PopulationPPO do alike outside a rollout: the normalize_obs option, the first observation, and the part of
+    a checkpoint that does not depend on how the parameters are kept."""
+
+    def _set_normalize(self, env, normalize_obs, policy_in_step=False):
+        """normalize_obs needs the rows between the env and the policy: not with the policy inside the env's launches."""
+        self.normalize_obs = bool(normalize_obs)
+        if not self.normalize_obs:
+            return
+        if policy_in_step:
+            raise ValueError("normalize_obs=True cannot be combined with policy_in_step=True: the policy inside the env's launches "
+                             "(pcc_rollout) reads the raw observation rows, not the normalised ones")
+        if hasattr(env, "groups"):
+            raise ValueError("normalize_obs=True is not supported over a GroupedNetworkEnv: its groups are stepped on their own streams "
+                             "and the policy reads the raw observation rows there")
+
+    def _first_obs(self, members, clip_obs, norm_eps):
+        """Reset the env; with normalize_obs every member gets its own moments of its own columns (obsnorm.ObsNormalizer)."""
+        self.obs = self.env.reset().clone()
+        if self.normalize_obs:
+            self.obs_norm = ObsNormalizer(self.env.obs_dim, members, clip_obs, norm_eps, device=self.env.device)
+            self.raw_obs = self.obs
+            self.obs = self.obs_norm.normalise(self.raw_obs)
+
+    def _adam_state(self):
+        return dict(flat=self.flat.detach().clone(), adam_m=self.adam_m.clone(), adam_v=self.adam_v.clone(), adam_t=int(self.adam_t))
+
+    def _load_adam_state(self, sd):
+        with torch.no_grad():
+            self.flat.copy_(sd["flat"])   # (the modules' parameters are views of it: share_flat)
+            self.adam_m.copy_(sd["adam_m"])
+            self.adam_v.copy_(sd["adam_v"])
+        self.adam_t = int(sd["adam_t"])
+
+    def _common_state(self):
+        """The keys both state_dict()s end with: the observation the next rollout starts from, torch's CPU and device generator
+        states (the rollout's noise and the minibatch permutations come from the device's), the env's snapshot, and with
+        normalize_obs the normaliser and the raw observation (without it the keys are what they were before the option)."""
+        dev = torch.device(self.env.device)
+        sd = {"obs": self.obs.detach().clone(), "torch_rng": torch.get_rng_state(),
+              "device_rng": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None, "env": self.env.snapshot()}
+        if self.normalize_obs:
+            sd.update(normalize_obs=True, obs_norm=self.obs_norm.state_dict(), raw_obs=self.raw_obs.detach().clone())
+        return sd
+
+    def _restore(self, sd):
+        """What both load_state_dict()s do after their own checks: the env from its snapshot (it must have been reset once: the
+        constructor did that), the parameters and the optimiser (self._load_params), the observation, the generator states."""
+        dev = torch.device(self.env.device)
+        theirs = bool(sd.get("normalize_obs", False))
+        if theirs != self.normalize_obs:
+            raise ValueError("the checkpoint was written with normalize_obs=%s, this object has normalize_obs=%s: weights without "
+                             "their normaliser are meaningless" % (theirs, self.normalize_obs))
+        self.env.restore(sd["env"])
+        self._load_params(sd)
+        self.obs = sd["obs"].to(dev).clone()
+        if self.normalize_obs:
+            self.obs_norm.load_state_dict(sd["obs_norm"])
+            self.raw_obs = sd["raw_obs"].to(dev).clone()
+        torch.set_rng_state(sd["torch_rng"].cpu())
+        if dev.type == "cuda" and sd.get("device_rng") is not None:
+            torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)
 
 
-class PPO(object):
+class PPO(_Trainer):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
                  epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
                  normalize_obs=False, clip_obs=10.0, norm_eps=1e-8):
@@ -233,13 +330,10 @@ class PPO(object):
             raise ValueError("PPO(policy_in_step=True) runs the policy inside the env's HIP launches: it needs the env on the GPU "
                              "(device=%r)" % (env.device,))
         self.policy_in_step = bool(policy_in_step)
-        self.normalize_obs = bool(normalize_obs)
-        _refuse_normalize(self.normalize_obs, policy_in_step, env)
+        self._set_normalize(env, normalize_obs, policy_in_step)
         self.env, self.gamma, self.lam, self.clip, self.ent_coef = env, gamma, lam, clip, ent_coef
         self.epochs, self.minibatch, self.horizon = epochs, minibatch, horizon
         torch.manual_seed(seed)
-        if hasattr(env, "groups"):   # GroupedNetworkEnv: the surface of a BatchedNetworkEnv, from its groups
-            env.obs_dim, env.n_senders = env.groups[0].obs_dim, env.groups[0].n_senders
         self.policy = MlpPolicy(env.obs_dim, 1, arch).to(env.device)
         if hasattr(env, "groups") and not (len(arch) == 2 and env.n_senders == 1 and torch.device(env.device).type == "cuda"):
             # (a GroupedNetworkEnv is stepped group by group on its streams by the fused rollout only: it has no step() of its own)
@@ -252,18 +346,12 @@ class PPO(object):
             _warn_once("PPO.update runs autograd + torch.optim.Adam (no pcc_ppo_minibatch_step for observation length %d, hidden %s, "
                        "%d sender(s) on %s): about 20x slower than the fused step" % (env.obs_dim, list(arch), env.n_senders, env.device))
         if self.fused_update:
-            from .native import lib
             self.flat = self.policy.share_flat()
             self.adam_m, self.adam_v, self.adam_t = torch.zeros_like(self.flat), torch.zeros_like(self.flat), 0
             self.scratch = torch.empty(lib().pcc_ppo_scratch_floats(env.obs_dim, arch[0], arch[1]), device=env.device)
             self.stats_buf = torch.zeros(4, device=env.device)
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=lr, eps=self.adam_eps)
-        self.obs = env.reset().clone()
-        if self.normalize_obs:
-            from .obsnorm import ObsNormalizer
-            self.obs_norm = ObsNormalizer(env.obs_dim, 1, clip_obs, norm_eps, device=env.device)
-            self.raw_obs = self.obs
-            self.obs = self.obs_norm.normalise(self.raw_obs)
+        self._first_obs(1, clip_obs, norm_eps)
         if self.minibatch is None:
             self.minibatch = max(2048, env.n_envs * horizon // 4)
 
@@ -272,7 +360,6 @@ class PPO(object):
         hidden = self.policy.hidden
         if not (torch.device(env.device).type == "cuda" and hidden is not None and env.n_senders == 1):
             return False
-        from .native import lib
         return lib().pcc_ppo_supported(int(env.obs_dim), hidden[0], hidden[1]) == 1
 
     def collect(self):
@@ -280,111 +367,88 @@ class PPO(object):
         writes action / log-probability / value into the rollout rows; the env reads that action row and writes the next
         observation, reward and done rows: two library calls and three kernels per step, no framework launch, no copy."""
         env, T, N = self.env, self.horizon, self.env.n_envs
-        dev = env.device
-        obs_b = torch.empty((T + 1, N, env.obs_dim), device=dev)   # row t: what the policy saw at step t; row T: the last
-        act_b = torch.empty((T, N, 1), device=dev)
-        logp_b = torch.empty((T, N), device=dev)
-        val_b = torch.empty((T, N), device=dev)
-        rew_b = torch.empty((T, N), device=dev)
-        done_b = torch.empty((T, N), dtype=torch.bool, device=dev)
-        if self.normalize_obs:
-            # the env writes raw rows; after each step ONE normalise launch fills the row the policy reads.  The statistics are
-            # frozen during the rollout: logp_old, the values and the update all see the same inputs.
-            norm = self.obs_norm
-            raw_b = torch.empty((T + 1, N, env.obs_dim), device=dev)
-            raw_b[0] = self.raw_obs
-            norm.normalise(raw_b[0], obs_b[0])
-        else:
-            obs_b[0] = self.obs
-        fused = self.policy.fused_ok(obs_b[0]) and env.n_senders == 1
-        groups = getattr(env, "groups", None)
+        rows = _RolloutRows(self, T, N)
+        fused = self.policy.fused_ok(rows.obs[0]) and env.n_senders == 1
         if self.policy_in_step and not fused:
             raise ValueError("PPO(policy_in_step=True) needs the fused rollout: a two-hidden-layer policy, one sender, on the GPU")
-        if self.policy_in_step:
-            # the whole horizon as one pcc_rollout per env (group): the same noise, parameters and rows as the loop below
-            arch = self.policy.hidden
-            params = self.policy.flat_params()
-            noise = torch.randn((T, N), device=dev)
-            u8 = done_b.view(torch.uint8)
-            if groups is None:
-                env.rollout(params, noise, obs_b, act_b, logp_b, val_b, rew_b, u8, arch=arch)
-            else:
-                n = env.group_size
-                cur = torch.cuda.current_stream(dev)
-                # (a group's rows of [T(+1), N] buffers are strided: each group fills contiguous buffers of its own on its stream)
-                parts = []
-                for g, eg in enumerate(groups):
-                    lo, hi = g * n, (g + 1) * n
-                    env.streams[g].wait_stream(cur)
-                    with torch.cuda.stream(env.streams[g]):
-                        ob = torch.empty((T + 1, n, env.obs_dim), device=dev)
-                        ob[0] = obs_b[0, lo:hi]
-                        bufs = (torch.empty((T, n, 1), device=dev), torch.empty((T, n), device=dev), torch.empty((T, n), device=dev),
-                                torch.empty((T, n), device=dev), torch.empty((T, n), dtype=torch.uint8, device=dev))
-                        eg.rollout(params, noise[:, lo:hi].contiguous(), ob, *bufs, arch=arch)
-                        parts.append((lo, hi, ob, bufs))
-                for g, (lo, hi, ob, bufs) in enumerate(parts):
-                    cur.wait_stream(env.streams[g])
-                    obs_b[1:, lo:hi] = ob[1:]
-                    for dst, src in zip((act_b, logp_b, val_b, rew_b, u8), bufs):
-                        dst[:, lo:hi] = src
-                    for tns in (ob,) + bufs:
-                        tns.record_stream(cur)
-        elif fused and groups is not None:
-            # Double-buffered sampling (GroupedNetworkEnv: the same envs as G groups on their own streams): group g's
-            # policy kernel and env step are queued on stream g, nothing joins the groups inside the rollout -- while one
-            # group's env launches run out their tails (a third of the wavefront slots busy, DESIGN.md section 4.1), the
-            # other group's policy kernel and launches fill the machine.  Same numbers as one batch: a group holds the
-            # global env ids g * n .. and reads its own rows of every buffer.
-            params = self.policy.flat_params()
-            noise = torch.randn((T, N), device=dev)
-            n = env.group_size
-            cur = torch.cuda.current_stream(dev)
-            for s in env.streams:
-                s.wait_stream(cur)                                 # the buffers and the noise were made on this stream
-            for t in range(T):
-                for g, eg in enumerate(groups):
-                    lo, hi = g * n, (g + 1) * n
-                    with torch.cuda.stream(env.streams[g]):
-                        self.policy.act_fused(obs_b[t, lo:hi], True, params, noise[t, lo:hi],
-                                              (act_b[t, lo:hi].reshape(n), logp_b[t, lo:hi], val_b[t, lo:hi]))
-                        eg.step_into(act_b[t, lo:hi], obs_b[t + 1, lo:hi], rew_b[t, lo:hi], done_b[t, lo:hi])
-            for s in env.streams:
-                cur.wait_stream(s)
-        elif fused:
-            params = self.policy.flat_params()                     # once per rollout, not per step
-            noise = torch.randn((T, N), device=dev)                # the horizon's draws in one launch
-            for t in range(T):
-                self.policy.act_fused(obs_b[t], True, params, noise[t], (act_b[t].reshape(N), logp_b[t], val_b[t]))
-                if self.normalize_obs:
-                    env.step_into(act_b[t], raw_b[t + 1], rew_b[t], done_b[t])
-                    norm.normalise(raw_b[t + 1], obs_b[t + 1])
-                else:
-                    env.step_into(act_b[t], obs_b[t + 1], rew_b[t], done_b[t])   # tensors in, tensors out, no host round trip
+        if not fused:
+            self._rollout_framework(rows)
         else:
-            for t in range(T):
-                a, logp, v = self.policy.act(obs_b[t])
-                act_b[t], logp_b[t], val_b[t] = a, logp, v
-                nobs, r, d, _ = env.step(a)
-                if self.normalize_obs:
-                    raw_b[t + 1] = nobs
-                    norm.normalise(raw_b[t + 1], obs_b[t + 1])
-                else:
-                    obs_b[t + 1] = nobs
-                rew_b[t], done_b[t] = r, d
-        obs = obs_b[T]
-        self.obs = obs.clone()
-        if self.normalize_obs:
-            self.raw_b, self.raw_obs = raw_b, raw_b[T].clone()
-            norm.update(raw_b[:T])   # rows 0 .. T - 1: what the policy saw
-        obs_b = obs_b[:T]
+            params = self.policy.flat_params()                     # once per rollout, not per step (a 13-tensor torch.cat)
+            noise = torch.randn((T, N), device=env.device)         # the horizon's draws in one launch
+            if self.policy_in_step:
+                self._rollout_in_step(rows, params, noise)
+            elif hasattr(env, "groups"):
+                self._rollout_double_buffered(rows, params, noise)
+            else:
+                rows.run(env, noise, lambda o, z, a, logp, v: self.policy.act_fused(o, True, params, z, (a, logp, v)))
+        obs = rows.finish(self)
         with torch.no_grad():
             last_v = self.policy.value(obs)
         # never train on corrupted rollouts: an overflowed in-flight ring / an empty ring pool (a trained
         # policy can push many deep-queue envs to MAX_RATE: BatchedNetworkEnv(ring_pools=...)) is flagged, not silent
         env.check_flags()
-        adv, ret = (gae_fused if fused else gae)(rew_b, val_b, done_b, last_v, self.gamma, self.lam)
-        return obs_b, act_b, logp_b, adv, ret, rew_b
+        adv, ret = (gae_fused if fused else gae)(rows.rew, rows.val, rows.done, last_v, self.gamma, self.lam)
+        return rows.obs[:T], rows.act, rows.logp, adv, ret, rows.rew
+
+    def _rollout_in_step(self, rows, params, noise):
+        """The whole horizon as one pcc_rollout per env (group): the same noise, parameters and rows as the fused loop."""
+        env, T, arch = self.env, rows.T, self.policy.hidden
+        dev = env.device
+        outs = (rows.act, rows.logp, rows.val, rows.rew, rows.done.view(torch.uint8))
+        if not hasattr(env, "groups"):
+            return env.rollout(params, noise, rows.obs, *outs, arch=arch)
+        n = env.group_size
+        cur = torch.cuda.current_stream(dev)
+        # (a group's rows of [T(+1), N] buffers are strided: each group fills contiguous buffers of its own on its stream)
+        parts = []
+        for g, eg in enumerate(env.groups):
+            lo, hi = g * n, (g + 1) * n
+            env.streams[g].wait_stream(cur)
+            with torch.cuda.stream(env.streams[g]):
+                ob = torch.empty((T + 1, n, env.obs_dim), device=dev)
+                ob[0] = rows.obs[0, lo:hi]
+                bufs = (torch.empty((T, n, 1), device=dev), torch.empty((T, n), device=dev), torch.empty((T, n), device=dev),
+                        torch.empty((T, n), device=dev), torch.empty((T, n), dtype=torch.uint8, device=dev))
+                eg.rollout(params, noise[:, lo:hi].contiguous(), ob, *bufs, arch=arch)
+                parts.append((lo, hi, ob, bufs))
+        for g, (lo, hi, ob, bufs) in enumerate(parts):
+            cur.wait_stream(env.streams[g])
+            rows.obs[1:, lo:hi] = ob[1:]
+            for dst, src in zip(outs, bufs):
+                dst[:, lo:hi] = src
+            for tns in (ob,) + bufs:
+                tns.record_stream(cur)
+
+    def _rollout_double_buffered(self, rows, params, noise):
+        """Double-buffered sampling (GroupedNetworkEnv: the same envs as G groups on their own streams): group g's policy
+        kernel and env step are queued on stream g, nothing joins the groups inside the rollout -- while one group's env launches
+        run out their tails (a third of the wavefront slots busy), the other group's policy kernel and
+        launches fill the machine.  Same numbers as one batch: a group holds the global env ids g * n .. and reads its own
+        rows of every buffer."""
+        env, n = self.env, self.env.group_size
+        cur = torch.cuda.current_stream(env.device)
+        for s in env.streams:
+            s.wait_stream(cur)                                 # the buffers and the noise were made on this stream
+        for t in range(rows.T):
+            for g, eg in enumerate(env.groups):
+                lo, hi = g * n, (g + 1) * n
+                with torch.cuda.stream(env.streams[g]):
+                    self.policy.act_fused(rows.obs[t, lo:hi], True, params, noise[t, lo:hi],
+                                          (rows.act[t, lo:hi].reshape(n), rows.logp[t, lo:hi], rows.val[t, lo:hi]))
+                    eg.step_into(rows.act[t, lo:hi], rows.obs[t + 1, lo:hi], rows.rew[t, lo:hi], rows.done[t, lo:hi])
+        for s in env.streams:
+            cur.wait_stream(s)
+
+    def _rollout_framework(self, rows):
+        """The policy as a torch module and env.step(): for a policy or an env that pcc_policy_act does not cover."""
+        for t in range(rows.T):
+            a, logp, v = self.policy.act(rows.obs[t])
+            rows.act[t], rows.logp[t], rows.val[t] = a, logp, v
+            nobs, r, d, _ = self.env.step(a)
+            rows.dst[t + 1] = nobs
+            rows.stepped(t)
+            rows.rew[t], rows.done[t] = r, d
 
     def update(self, obs_b, act_b, logp_b, adv, ret):
         n = obs_b.shape[0] * obs_b.shape[1]
@@ -409,7 +473,6 @@ class PPO(object):
     def minibatch_step_fused(self, obs_f, act_f, logp_f, adv_f, ret_f, perm, start, count, lr=None, grad_out=None):
         """One optimiser step on samples perm[start : start + count] of the flattened rollout as two launches of the HIP
         library (include/pcc_policy.h: pcc_ppo_minibatch_step).  lr=0: gradient only (into grad_out)."""
-        from .native import lib
         lr = self.lr if lr is None else lr
         if start < 0 or count < 1 or start + count > (perm.numel() if perm is not None else obs_f.shape[0]):
             raise ValueError("minibatch [%d, %d) outside the rollout" % (start, start + count))
@@ -417,13 +480,10 @@ class PPO(object):
             self.adam_t += 1
         D = obs_f.shape[1]
         h1, h2 = self.policy.hidden
-        rc = lib().pcc_ppo_minibatch_step(_ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), start, count,
-                                          D, h1, h2, _ptr(self.flat), _ptr(self.adam_m), _ptr(self.adam_v), max(self.adam_t, 1),
-                                          lr, 0.9, 0.999, self.adam_eps, self.clip, self.ent_coef, _ptr(self.scratch),
-                                          _ptr(grad_out), _ptr(self.stats_buf),
-                                          ctypes.c_void_p(torch.cuda.current_stream(obs_f.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError("pcc_ppo_minibatch_step failed (%d)" % rc)
+        call("pcc_ppo_minibatch_step", _ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), start, count,
+             D, h1, h2, _ptr(self.flat), _ptr(self.adam_m), _ptr(self.adam_v), max(self.adam_t, 1),
+             lr, 0.9, 0.999, self.adam_eps, self.clip, self.ent_coef, _ptr(self.scratch),
+             _ptr(grad_out), _ptr(self.stats_buf), current_stream(obs_f.device))
 
     def _update_fused(self, obs_f, act_f, logp_f, adv_f, ret_f):
         n = obs_f.shape[0]
@@ -440,51 +500,34 @@ class PPO(object):
     def state_dict(self):
         """Everything the next iterate() depends on, for a checkpoint that resumes bit for bit: the parameters and Adam's state (the
         flat block with m, v, t on the fused path, the module's and the torch optimiser's state_dict on the framework path), the
-        observation the next rollout starts from, torch's CPU and device generator states (the rollout's noise and the
-        minibatch permutations come from the device's), and the env's snapshot (BatchedNetworkEnv.snapshot: not with the env options it
-        refuses).  torch.save() takes it as it is."""
-        dev = torch.device(self.env.device)
-        sd = {"format": 1, "fused_update": self.fused_update, "obs_dim": int(self.env.obs_dim), "n_envs": int(self.env.n_envs),
-              "obs": self.obs.detach().clone(), "torch_rng": torch.get_rng_state(),
-              "device_rng": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None, "env": self.env.snapshot()}
+        observation, the generator states and the env's snapshot (_Trainer._common_state; BatchedNetworkEnv.snapshot: not with the env
+        options it refuses).  torch.save() takes it as it is."""
+        sd = {"format": 1, "fused_update": self.fused_update, "obs_dim": int(self.env.obs_dim), "n_envs": int(self.env.n_envs)}
         if self.fused_update:
-            sd.update(flat=self.flat.detach().clone(), adam_m=self.adam_m.clone(), adam_v=self.adam_v.clone(), adam_t=int(self.adam_t))
+            sd.update(self._adam_state())
         else:
             sd.update(policy={k: v.detach().clone() for k, v in self.policy.state_dict().items()}, opt=self.opt.state_dict())
-        if self.normalize_obs:   # (without it the keys are what they were)
-            sd.update(normalize_obs=True, obs_norm=self.obs_norm.state_dict(), raw_obs=self.raw_obs.detach().clone())
+        sd.update(self._common_state())
         return sd
 
     def load_state_dict(self, sd):
-        """Continue from a state_dict() of a PPO of the same construction (env configuration, arch, update path): the env is restored
-        from its snapshot (it must have been reset once: the constructor did that), then the parameters, the optimiser, the
-        observation and the generator states."""
-        dev = torch.device(self.env.device)
+        """Continue from a state_dict() of a PPO of the same construction (env configuration, arch, update path, normalize_obs):
+        _Trainer._restore after the checks."""
         if sd.get("format") != 1:
             raise ValueError("not a PPO.state_dict() of this version")
         if bool(sd["fused_update"]) != self.fused_update or sd["obs_dim"] != int(self.env.obs_dim) or sd["n_envs"] != int(self.env.n_envs):
             raise ValueError("the checkpoint is of another PPO: fused_update=%s, obs_dim=%d, n_envs=%d; this one: %s, %d, %d"
                              % (sd["fused_update"], sd["obs_dim"], sd["n_envs"], self.fused_update, self.env.obs_dim, self.env.n_envs))
-        _check_normalize(sd, self.normalize_obs)
         if self.fused_update and sd["flat"].numel() != self.flat.numel():
             raise ValueError("the checkpoint's policy has %d parameters, this one %d (another --arch)" % (sd["flat"].numel(), self.flat.numel()))
-        self.env.restore(sd["env"])
+        self._restore(sd)
+
+    def _load_params(self, sd):
         if self.fused_update:
-            with torch.no_grad():
-                self.flat.copy_(sd["flat"])   # (the module's parameters are views of it: share_flat)
-                self.adam_m.copy_(sd["adam_m"])
-                self.adam_v.copy_(sd["adam_v"])
-            self.adam_t = int(sd["adam_t"])
+            self._load_adam_state(sd)
         else:
             self.policy.load_state_dict(sd["policy"])
             self.opt.load_state_dict(sd["opt"])
-        self.obs = sd["obs"].to(dev).clone()
-        if self.normalize_obs:
-            self.obs_norm.load_state_dict(sd["obs_norm"])
-            self.raw_obs = sd["raw_obs"].to(dev).clone()
-        torch.set_rng_state(sd["torch_rng"].cpu())
-        if dev.type == "cuda" and sd.get("device_rng") is not None:
-            torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)
 
     def iterate(self):
         obs_b, act_b, logp_b, adv, ret, rew = self.collect()
@@ -544,7 +587,22 @@ def explore_matrix(factors=(0.8, 1.2), explore=("lr", "ent_coef"), bounds=None):
     return rows
 
 
-class PopulationPPO(object):
+def _hyper_columns(members, **named):
+    """lr, clip, ent_coef, gamma, lam -- each a scalar (a number, a numpy scalar, a 0-dim tensor) or one value per member -- as
+    `members` rows of `hyper`."""
+    cols = []
+    for name in HYPER_NAMES:
+        try:
+            vals = [float(named[name])] * members
+        except (TypeError, ValueError):
+            vals = [float(x) for x in named[name]]
+        if len(vals) != members:
+            raise ValueError("PopulationPPO: %s has %d values for %d members" % (name, len(vals), members))
+        cols.append(vals)
+    return [list(r) + [0.0] * (HYPER_COLS - len(HYPER_NAMES)) for r in zip(*cols)]
+
+
+class PopulationPPO(_Trainer):
     """`members` independent PPO learners -- each its own policy, Adam state and hyper-parameters -- on `members` equal slices
     of ONE BatchedNetworkEnv: the env is stepped once per step for the whole batch, and the policy forward, the advantage
     estimation and the optimiser step are each one library call for all members (include/pcc_policy.h: pcc_policy_act_pop,
@@ -557,26 +615,15 @@ class PopulationPPO(object):
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
                  epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8):
-        from .env import BatchedNetworkEnv
-        from .native import lib
         members = int(members)
-        self.normalize_obs = bool(normalize_obs)
-        _refuse_normalize(self.normalize_obs, False, env)
+        self._set_normalize(env, normalize_obs)
         if members < 1 or members > 1024:
             raise ValueError("PopulationPPO: members = %d (1 .. 1024)" % members)
         if len(arch) != 2:
             raise ValueError("PopulationPPO needs a policy of two hidden layers (arch = %r)" % (tuple(arch),))
         if int(env.n_envs) % members != 0:
             raise ValueError("PopulationPPO: %d envs do not divide into %d members" % (env.n_envs, members))
-        cols = []
-        for name, v in (("lr", lr), ("clip", clip), ("ent_coef", ent_coef), ("gamma", gamma), ("lam", lam)):
-            try:
-                vals = [float(v)] * members          # a scalar: a number, a numpy scalar, a 0-dim tensor
-            except (TypeError, ValueError):
-                vals = [float(x) for x in v]
-            if len(vals) != members:
-                raise ValueError("PopulationPPO: %s has %d values for %d members" % (name, len(vals), members))
-            cols.append(vals)
+        self.hyper_rows = _hyper_columns(members, lr=lr, clip=clip, ent_coef=ent_coef, gamma=gamma, lam=lam)
         seeds = list(range(members)) if seeds is None else [int(x) for x in seeds]
         if len(seeds) != members:
             raise ValueError("PopulationPPO: seeds has %d values for %d members" % (len(seeds), members))
@@ -589,7 +636,6 @@ class PopulationPPO(object):
         self.epochs, self.horizon, self.adam_eps = epochs, horizon, 1e-5
         self.n_member = int(env.n_envs) // members
         dev = env.device
-        self.hyper_rows = [list(r) + [0.0] * (HYPER_COLS - 5) for r in zip(*cols)]
         self.hyper = torch.tensor(self.hyper_rows, dtype=torch.float32, device=dev)
         self.generation = 0   # evolve() calls so far: the Philox counter of the next one
         D = int(env.obs_dim)
@@ -606,36 +652,25 @@ class PopulationPPO(object):
         self.scratch_floats = lib().pcc_ppo_scratch_floats(D, *self.arch)
         self.scratch = torch.empty(members * self.scratch_floats, device=dev)
         self.stats_buf = torch.zeros((members, 4), device=dev)
-        self.obs = env.reset().clone()
-        if self.normalize_obs:   # every member its own moments of its own columns (obsnorm.ObsNormalizer)
-            from .obsnorm import ObsNormalizer
-            self.obs_norm = ObsNormalizer(D, members, clip_obs, norm_eps, device=dev)
-            self.raw_obs = self.obs
-            self.obs = self.obs_norm.normalise(self.raw_obs)
+        self._first_obs(members, clip_obs, norm_eps)
         per_member = self.n_member * horizon
         self.minibatch = min(per_member, max(2048, per_member // 4)) if minibatch is None else int(minibatch)
 
     def _stream(self):
-        return ctypes.c_void_p(torch.cuda.current_stream(self.env.device).cuda_stream)
+        return current_stream(self.env.device)
 
     def _act(self, obs, noise, act, logp, val):
         """The policies on one [N, D] observation row: member m on its slice with its parameters, one launch."""
-        from .native import lib
         N, D = obs.shape
-        rc = lib().pcc_policy_act_pop(_ptr(obs), N, D, _ptr(self.flat), self.param_stride, self.members, self.arch[0], self.arch[1],
-                                      _ptr(noise), None, _ptr(act), _ptr(logp), _ptr(val), self._stream())
-        if rc != 0:
-            raise RuntimeError("pcc_policy_act_pop failed (%d)" % rc)
+        call("pcc_policy_act_pop", _ptr(obs), N, D, _ptr(self.flat), self.param_stride, self.members, self.arch[0], self.arch[1],
+             _ptr(noise), None, _ptr(act), _ptr(logp), _ptr(val), self._stream())
 
     def _gae(self, rew_b, val_b, done_b, last_v):
-        from .native import lib
         T, N = rew_b.shape
         adv, ret = torch.empty_like(rew_b), torch.empty_like(rew_b)
         d8 = done_b.view(torch.uint8)
-        rc = lib().pcc_gae_pop(_ptr(rew_b), _ptr(val_b), _ptr(d8), _ptr(last_v), T, N, self.members, _ptr(self.hyper), _ptr(adv), _ptr(ret),
-                               self._stream())
-        if rc != 0:
-            raise RuntimeError("pcc_gae_pop failed (%d)" % rc)
+        call("pcc_gae_pop", _ptr(rew_b), _ptr(val_b), _ptr(d8), _ptr(last_v), T, N, self.members, _ptr(self.hyper), _ptr(adv), _ptr(ret),
+             self._stream())
         return adv, ret
 
     def collect(self, noise=None):
@@ -644,38 +679,16 @@ class PopulationPPO(object):
         [horizon, n_envs] standard-normal draws (default: drawn here).  Returns PPO.collect()'s tuple; the value and done rows
         stay in self.val_b / self.done_b."""
         env, T, N = self.env, self.horizon, int(self.env.n_envs)
-        dev = env.device
-        obs_b = torch.empty((T + 1, N, env.obs_dim), device=dev)
-        act_b = torch.empty((T, N, 1), device=dev)
-        logp_b, val_b, rew_b = (torch.empty((T, N), device=dev) for _ in range(3))
-        done_b = torch.empty((T, N), dtype=torch.bool, device=dev)
-        if self.normalize_obs:   # as PPO.collect: raw rows from the env, one normalise launch per step, frozen statistics
-            norm = self.obs_norm
-            raw_b = torch.empty((T + 1, N, env.obs_dim), device=dev)
-            raw_b[0] = self.raw_obs
-            norm.normalise(raw_b[0], obs_b[0])
-        else:
-            obs_b[0] = self.obs
+        rows = _RolloutRows(self, T, N)
         if noise is None:
-            noise = torch.randn((T, N), device=dev)
-        for t in range(T):
-            self._act(obs_b[t], noise[t], act_b[t].reshape(N), logp_b[t], val_b[t])
-            if self.normalize_obs:
-                env.step_into(act_b[t], raw_b[t + 1], rew_b[t], done_b[t])
-                norm.normalise(raw_b[t + 1], obs_b[t + 1])
-            else:
-                env.step_into(act_b[t], obs_b[t + 1], rew_b[t], done_b[t])
-        self.obs = obs_b[T].clone()
-        if self.normalize_obs:
-            self.raw_b, self.raw_obs = raw_b, raw_b[T].clone()
-        last_v = torch.empty(N, device=dev)
-        self._act(obs_b[T], None, None, None, last_v)
+            noise = torch.randn((T, N), device=env.device)
+        rows.run(env, noise, self._act)
+        last_v = torch.empty(N, device=env.device)
+        self._act(rows.finish(self), None, None, None, last_v)
         env.check_flags()
-        adv, ret = self._gae(rew_b, val_b, done_b, last_v)
-        self.val_b, self.done_b = val_b, done_b
-        if self.normalize_obs:
-            norm.update(raw_b[:T])   # rows 0 .. T - 1: what the policies saw
-        return obs_b[:T], act_b, logp_b, adv, ret, rew_b
+        adv, ret = self._gae(rows.rew, rows.val, rows.done, last_v)
+        self.val_b, self.done_b = rows.val, rows.done
+        return rows.obs[:T], rows.act, rows.logp, adv, ret, rows.rew
 
     def normalise(self, adv):
         return normalise_per_member(adv, self.members)
@@ -683,17 +696,14 @@ class PopulationPPO(object):
     def minibatch_step(self, obs_f, act_f, logp_f, adv_f, ret_f, perm, start, count, grad_out=None):
         """One optimiser step of every member on its samples perm[m][start : start + count] (global indices into the flattened
         rollout): two launches (pcc_ppo_minibatch_step_pop)."""
-        from .native import lib
         if start < 0 or count < 1 or start + count > perm.shape[1]:
             raise ValueError("minibatch [%d, %d) outside a member's rollout" % (start, start + count))
         self.adam_t += 1
         D = obs_f.shape[1]
-        rc = lib().pcc_ppo_minibatch_step_pop(_ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), perm.stride(0),
-                                              start, count, D, self.arch[0], self.arch[1], _ptr(self.flat), _ptr(self.adam_m),
-                                              _ptr(self.adam_v), self.param_stride, self.members, _ptr(self.hyper), self.adam_t, 0.9, 0.999,
-                                              self.adam_eps, _ptr(self.scratch), _ptr(grad_out), _ptr(self.stats_buf), self._stream())
-        if rc != 0:
-            raise RuntimeError("pcc_ppo_minibatch_step_pop failed (%d)" % rc)
+        call("pcc_ppo_minibatch_step_pop", _ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), perm.stride(0),
+             start, count, D, self.arch[0], self.arch[1], _ptr(self.flat), _ptr(self.adam_m),
+             _ptr(self.adam_v), self.param_stride, self.members, _ptr(self.hyper), self.adam_t, 0.9, 0.999,
+             self.adam_eps, _ptr(self.scratch), _ptr(grad_out), _ptr(self.stats_buf), self._stream())
 
     def update(self, obs_b, act_b, logp_b, adv, ret, perms=None):
         """`epochs` passes over every member's own samples in minibatches of self.minibatch samples per member.  perms: one
@@ -728,7 +738,6 @@ class PopulationPPO(object):
         The draws are Philox's of (seed, self.generation, member): a run repeats and resumes bit for bit.  Returns (parent, rank)
         as device int32 tensors -- parent[m] == m for a member that was not replaced -- without synchronising.  The host mirror
         hyper_rows is stale from here on (None): hypers() reads the rows back."""
-        from .native import lib
         if not 0.0 <= frac <= 0.5:
             raise ValueError("evolve: frac = %r (0 .. 0.5: the worst members are replaced from as many of the best)" % (frac,))
         dev = self.env.device
@@ -738,11 +747,9 @@ class PopulationPPO(object):
         ex = torch.tensor(explore_matrix(factors, explore, bounds), dtype=torch.float32, device=dev)
         parent = torch.empty(self.members, dtype=torch.int32, device=dev)
         rank = torch.empty(self.members, dtype=torch.int32, device=dev)
-        rc = lib().pcc_pbt_evolve(_ptr(score), self.members, int(frac * self.members), _ptr(self.flat), _ptr(self.adam_m), _ptr(self.adam_v),
-                                  self.param_stride, self.n_params, _ptr(self.hyper), _ptr(ex), int(seed) & 0xFFFFFFFFFFFFFFFF,
-                                  self.generation & 0xFFFFFFFF, _ptr(parent), _ptr(rank), self._stream())
-        if rc != 0:
-            raise RuntimeError("pcc_pbt_evolve failed (%d)" % rc)
+        call("pcc_pbt_evolve", _ptr(score), self.members, int(frac * self.members), _ptr(self.flat), _ptr(self.adam_m), _ptr(self.adam_v),
+             self.param_stride, self.n_params, _ptr(self.hyper), _ptr(ex), int(seed) & 0xFFFFFFFFFFFFFFFF,
+             self.generation & 0xFFFFFFFF, _ptr(parent), _ptr(rank), self._stream())
         if self.normalize_obs:   # weights without their normaliser are meaningless: a replaced member takes its parent's too
             self.obs_norm.inherit(parent)
         self.generation += 1
@@ -756,37 +763,24 @@ class PopulationPPO(object):
     def state_dict(self):
         """Everything the next iterate() depends on (PPO.state_dict's contract): the flat block, Adam's state and step, hyper, the
         observation, the generator states and the env's snapshot; and the generation the next evolve() draws with."""
-        dev = torch.device(self.env.device)
         sd = {"format": "population-1", "members": self.members, "obs_dim": int(self.env.obs_dim), "n_envs": int(self.env.n_envs),
-              "arch": self.arch, "flat": self.flat.detach().clone(), "adam_m": self.adam_m.clone(), "adam_v": self.adam_v.clone(),
-              "adam_t": int(self.adam_t), "generation": int(self.generation), "hyper": self.hyper.clone(), "obs": self.obs.detach().clone(),
-              "torch_rng": torch.get_rng_state(), "device_rng": torch.cuda.get_rng_state(dev), "env": self.env.snapshot()}
-        if self.normalize_obs:   # (without it the keys are what they were)
-            sd.update(normalize_obs=True, obs_norm=self.obs_norm.state_dict(), raw_obs=self.raw_obs.detach().clone())
+              "arch": self.arch, "generation": int(self.generation), "hyper": self.hyper.clone()}
+        sd.update(self._adam_state())
+        sd.update(self._common_state())
         return sd
 
     def load_state_dict(self, sd):
         """Continue from a state_dict() of a PopulationPPO of the same construction (env configuration, members, arch)."""
-        dev = torch.device(self.env.device)
         if sd.get("format") != "population-1":
             raise ValueError("not a PopulationPPO.state_dict() of this version")
         mine = (self.members, int(self.env.obs_dim), int(self.env.n_envs), tuple(self.arch))
         theirs = (sd["members"], sd["obs_dim"], sd["n_envs"], tuple(sd["arch"]))
         if mine != theirs:
             raise ValueError("the checkpoint is of another population: (members, obs_dim, n_envs, arch) = %s; this one: %s" % (theirs, mine))
-        _check_normalize(sd, self.normalize_obs)
-        self.env.restore(sd["env"])
-        with torch.no_grad():
-            self.flat.copy_(sd["flat"])       # (the policies' parameters are views of its rows)
-            self.adam_m.copy_(sd["adam_m"])
-            self.adam_v.copy_(sd["adam_v"])
-            self.hyper.copy_(sd["hyper"])
+        self._restore(sd)
+
+    def _load_params(self, sd):
+        self._load_adam_state(sd)
+        self.hyper.copy_(sd["hyper"])
         self.hyper_rows = [[float(x) for x in r] for r in self.hyper.tolist()]
-        self.adam_t = int(sd["adam_t"])
         self.generation = int(sd.get("generation", 0))   # (a checkpoint from before evolve() has none)
-        self.obs = sd["obs"].to(dev).clone()
-        if self.normalize_obs:
-            self.obs_norm.load_state_dict(sd["obs_norm"])
-            self.raw_obs = sd["raw_obs"].to(dev).clone()
-        torch.set_rng_state(sd["torch_rng"].cpu())
-        torch.cuda.set_rng_state(sd["device_rng"].cpu(), dev)

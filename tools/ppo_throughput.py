@@ -2,18 +2,20 @@
 """What the whole training loop costs next to the env alone (GPU box only):
 env-steps/s of (a) the env stepped with pre-generated actions, (b) the PPO rollout (policy forward +
 sampling + env step + buffers), (c) rollout + GAE + the PPO epochs, all at the bench size.
-   python tools/ppo_throughput.py [n_envs [horizon]] [--arch 64,32] [--history 3] [--features all | name,name,...]
+   python tools/ppo_throughput.py [n_envs [horizon]] [--arch 64,32] [--history 3] [--features all | name,name,...] [--window 1]
 (defaults: the reference's policy 32,16 on history 10 x the 3 default features; the per-shape comparison of the fused and the
-framework paths is tools/ppo_shapes.py)"""
+framework paths is tools/ppo_shapes.py; --window W times W times as many calls per figure: at a few hundred envs a rollout is
+milliseconds of host time and the default windows measure the clock)"""
 import argparse, json, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import pcc_rl_amd
-from pcc_rl_amd.ppo import PPO
+from pcc_rl_amd.ppo import PPO, PopulationPPO
 
 ap = argparse.ArgumentParser()
 ap.add_argument("n_envs", nargs="?", type=int, default=65536)
 ap.add_argument("horizon", nargs="?", type=int, default=64)
+ap.add_argument("--window", type=int, default=1)
 ap.add_argument("--arch", default="32,16")
 ap.add_argument("--history", type=int, default=None)
 ap.add_argument("--features", default=None)
@@ -31,6 +33,7 @@ env = pcc_rl_amd.BatchedNetworkEnv(N, device=dev, seed=0, **ENV_KW)
 agent = PPO(env, arch=ARCH, horizon=T, seed=0, minibatch=max(2048, N * T // 4))
 acts = torch.rand((T, N), device=dev) * 2 - 1
 def timed(fn, reps):
+    reps *= args.window
     fn(); torch.cuda.synchronize(); t0 = time.perf_counter()
     for _ in range(reps): fn()
     torch.cuda.synchronize(); return (time.perf_counter() - t0) / reps
@@ -46,6 +49,18 @@ t_upd = timed(update, 2)
 agent_fw = PPO(env, arch=ARCH, horizon=T, seed=0, minibatch=max(2048, N * T // 4), fused_update=False)
 def update_fw(): agent_fw.update(*batch["b"][:5])
 t_upd_fw = timed(update_fw, 1)
+# four learners on the same env (PopulationPPO: one library call per stage for all of them; tools/ppo_population.py has the variants)
+population = None
+if agent.fused_update:   # (PopulationPPO has no framework path)
+    pop = PopulationPPO(env, 4, arch=ARCH, horizon=T)
+    pbatch = {}
+    def rollout_p(): pbatch["b"] = pop.collect()
+    t_roll_p = timed(rollout_p, 3)
+    def update_p(): pop.update(*pbatch["b"][:5])
+    t_upd_p = timed(update_p, 2)
+    population = {"members": 4, "rollout_ms_per_step": 1e3 * t_roll_p / T, "update_s": t_upd_p, "minibatch_per_member": pop.minibatch,
+                  "rollout_plus_update_env_steps_per_s": N * T / (t_roll_p + t_upd_p)}
+    del pop, pbatch
 # the same rollout double-buffered: the envs as two groups on their own streams, a group's policy kernel and env step queued
 # on its stream, no join inside the rollout (PPO.collect over a GroupedNetworkEnv: bit-identical data, tests/test_ppo.py)
 env.close()
@@ -69,6 +84,7 @@ out = {"n_envs": N, "horizon": T,
                       "rollout_plus_update_env_steps_per_s": N * T / (t_roll_g + t_upd_g),
                       "note": "PPO.collect over GroupedNetworkEnv(N, 2): double-buffered sampling, the same data as one batch"},
        "framework_update": {"update_s": t_upd_fw, "rollout_plus_update_env_steps_per_s": N * T / (t_roll + t_upd_fw)},
+       "population": population, "calls_per_window_x": args.window,
        "note": "PPO with the reference script's policy shape and hyper-parameters (pi/vf MLP 32-16, minibatch 2048, 4 epochs); "
                "minibatch = N*T/4 keeps the reference's 4 minibatches per epoch (8192 samples / 2048) at this batch size"}
 print(json.dumps(out, indent=1))

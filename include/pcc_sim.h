@@ -304,7 +304,12 @@ int pcc_set_cwnd_mode(pcc_sim_t *sim, int enable);
  * more acknowledgements in one interval, raise PCC_FLAG_RING_OVERFLOW. */
 int pcc_set_latency_noise(pcc_sim_t *sim, int enable, double max_noise);
 
-/* DELTA_SCALE (src/common/config.py:17, default 0.025) and MAX_STEPS (ns:41, default 400) */
+/* DELTA_SCALE (src/common/config.py:17, default 0.025) and MAX_STEPS (ns:41, default 400).
+ * delta_scale must be finite and > 0; anything else (NaN, +-inf, 0, a negative value) is PCC_EINVAL and leaves the handle's
+ * value as it was.  The scaled action of a step is action * delta_scale: with a NaN scale, or a scale of 0 and an action of
+ * +-inf, it is NaN, which passes both rate clamps (neither comparison holds) -- 1 / rate is the gap between two SENDs, and the
+ * send loops would never end.  A negative scale would turn every action round.  Infinite ACTIONS are fine under a scale of this
+ * domain: the clamps absorb them (rate -> 40 or 1000 packets/s). */
 int pcc_set_delta_scale(pcc_sim_t *sim, double delta_scale);
 int pcc_set_max_steps(pcc_sim_t *sim, int max_steps);
 

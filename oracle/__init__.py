@@ -104,6 +104,11 @@ def lib():
             ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ip, ctypes.c_int,
             ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, _u64p,
             ctypes.c_long, _dp, ctypes.c_long, _dp, _dp, _dp, ctypes.c_double, _ip, _dp, _dp, _dp, _dp, _dp, ctypes.c_int]
+        L.pcc_oracle_run_batch_ranges.restype = ctypes.c_int
+        L.pcc_oracle_run_batch_ranges.argtypes = [
+            ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _ip, ctypes.c_int,
+            ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_uint64, ctypes.c_uint32, _u64p,
+            ctypes.c_long, _dp, ctypes.c_long, _dp, _dp, _dp, ctypes.c_double, _ip, _dp, _dp, _dp, _dp, _dp, _dp, _dp, ctypes.c_int]
         _lib = L
     return _lib
 
@@ -136,6 +141,13 @@ def metric_table():
     mn, mx, sc = (np.zeros(N_METRICS) for _ in range(3))
     lib().pcc_oracle_metric_table(_ptr(mn), _ptr(mx), _ptr(sc))
     return mn, mx, sc
+
+
+def _ranges(lo, hi):
+    lo, hi = (np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (lo, hi))
+    if lo.shape != (5,) or hi.shape != (5,):
+        raise ValueError("ranges are (lo, hi) of five values each: bw, latency, queue exponent, loss, rate0 / bw")
+    return lo, hi
 
 
 class OracleEnv(object):
@@ -175,6 +187,16 @@ class OracleEnv(object):
     def set_params(self, bw, dl, queue, loss, rate0):
         r = np.atleast_1d(np.asarray(rate0, dtype=np.float64))
         self.L.pcc_oracle_set_params(self.h, bw, dl, float(queue), loss, _ptr(r))
+
+    def set_ranges(self, lo, hi):
+        """The five ranges the next reset() samples from -- (bw, latency, queue exponent, loss, rate0 / bw), ns:355-358 and
+        455-466 -- as pcc_set_param_ranges takes them; an episode that is running goes on with its links."""
+        lo, hi = _ranges(lo, hi)
+        self.L.pcc_oracle_set_ranges(self.h, _ptr(lo), _ptr(hi))
+
+    def clear_params(self):
+        """Back from set_params() to sampling: the next reset() draws its links from the ranges again."""
+        self.L.pcc_oracle_clear_params(self.h)
 
     def reset(self):
         obs = np.zeros((self.n_senders, self.HF))
@@ -234,13 +256,14 @@ class OracleEnv(object):
 def run_batch(actions, n_senders=1, history_len=10, features=DEFAULT_FEATURES, mean_mode=MEAN_NUMPY,
               delta_scale=0.025, rng_mode=RNG_PHILOX, seed=0, env_gid_base=0, mt_seeds=None, mt_skip=5,
               trace=None, params=None, n_episodes=1, n_threads=None, want_obs=True, cwnd_actions=None,
-              latency_noise=None, first_episode=None):
+              latency_noise=None, first_episode=None, ranges=None):
     """Run B independent envs for T steps.  actions: [B, T] or [B, T, n_senders].
     cwnd_actions (same shape) switches the USE_CWND engine option on and supplies the second
     action component; latency_noise (e.g. 1.1 = the reference's MAX_LATENCY_NOISE) switches
     USE_LATENCY_NOISE on.  first_episode (an int or [B] ints, Philox uniforms only): the episode index env b starts at
     -- with Philox an episode's links and draws are keyed by (env id, episode index), so an env in its k-th episode can
-    be checked without replaying the k episodes before it.
+    be checked without replaying the k episodes before it.  ranges = (lo, hi), five values each: what every env's links
+    are sampled from where params is None (OracleEnv.set_ranges); None = the reference's ranges.
 
     Returns dict(steps [B, S, T, 19], obs [B, S, T, H*F], obs0 [B, S, H*F],
                  params [B, 5+S], warm [B, 2]); S axis squeezed when n_senders == 1.
@@ -267,10 +290,11 @@ def run_batch(actions, n_senders=1, history_len=10, features=DEFAULT_FEATURES, m
         if rng_mode != RNG_PHILOX:
             raise ValueError("first_episode needs Philox uniforms (the other streams depend on the episodes before)")
         fe = np.ascontiguousarray(np.broadcast_to(np.asarray(first_episode, dtype=np.int32), (B,)))
-    bad = lib().pcc_oracle_run_batch_at(
+    lo, hi = (None, None) if ranges is None else _ranges(*ranges)
+    bad = lib().pcc_oracle_run_batch_ranges(
         B, S, T, n_episodes, history_len, _ptr(fids, _ip), len(fids), mean_mode, delta_scale, rng_mode,
         int(seed), int(env_gid_base), _ptr(ms, _u64p), int(mt_skip), _ptr(tr),
-        0 if tr is None else tr.shape[1], _ptr(p), _ptr(a), _ptr(ca), float(latency_noise or 0.0), _ptr(fe, _ip), _ptr(steps),
+        0 if tr is None else tr.shape[1], _ptr(p), _ptr(a), _ptr(ca), float(latency_noise or 0.0), _ptr(fe, _ip), _ptr(lo), _ptr(hi), _ptr(steps),
         _ptr(obs), _ptr(obs0), _ptr(pout), _ptr(warm), nt)
     if bad:
         raise RuntimeError("loss-uniform trace ran out for env %d" % (bad - 1))

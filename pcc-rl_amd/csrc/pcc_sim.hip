@@ -1018,6 +1018,10 @@ int pcc_set_latency_noise(pcc_sim_t *sim, int enable, double max_noise) {
 
 int pcc_set_delta_scale(pcc_sim_t *sim, double delta_scale) {
     if (!sim) return fail(PCC_EINVAL, "sim is NULL");
+    // (a NaN scale, or 0 times an infinite action, is a NaN delta: both rate clamps let it through and 1 / rate is the SEND gap --
+    // the case reset_env describes for a bad rate0; every other way in is flagged and replaced, this one is refused here)
+    if (!(delta_scale > 0.0) || !(delta_scale <= 1.7976931348623157e308))
+        return fail(PCC_EINVAL, "delta_scale must be finite and > 0 (got %g): a scaled action of NaN would stall the send loops", delta_scale);
     sim->d.delta_scale = delta_scale;
     return PCC_OK;
 }

@@ -143,6 +143,9 @@ class BatchedNetworkEnv(object):
         self._ring_pools = None if ring_pools is None else tuple(int(v) for v in ring_pools)
         self._env_gid_base, self._ring_capacity = int(env_gid_base), int(ring_capacity) or DEFAULT_RING_CAPACITY
         self._delta_scale = float(DELTA_SCALE if delta_scale is None else delta_scale)
+        if not (0.0 < self._delta_scale < float("inf")):
+            # (pcc_set_delta_scale refuses the same, include/pcc_sim.h: said here before a handle exists)
+            raise ValueError("delta_scale must be finite and > 0 (got %r)" % (delta_scale,))
 
         L = lib()
         fids = (ctypes.c_int32 * len(self.feature_ids))(*self.feature_ids)
@@ -159,7 +162,7 @@ class BatchedNetworkEnv(object):
             check(L.pcc_set_ring_pools(self._h, *[int(v) for v in ring_pools]))
         self.set_tuning(list_min_envs=self.DEFAULT_LIST_MIN_ENVS, fused=self.DEFAULT_FUSED, fused_acquire=self.DEFAULT_FUSED_ACQUIRE,
                         noise_sorted=self.DEFAULT_NOISE_SORTED)
-        check(L.pcc_set_delta_scale(self._h, float(DELTA_SCALE if delta_scale is None else delta_scale)))
+        check(L.pcc_set_delta_scale(self._h, self._delta_scale))
         check(L.pcc_set_max_steps(self._h, self.max_steps))
         # the reference's dormant USE_CWND engine option (ns:54): window-limited sending, actions
         # become [rate action, cwnd action] (ns:376-377, 412-414)

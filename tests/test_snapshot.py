@@ -68,7 +68,7 @@ def assert_same_state(a, b):
 def dirty(env, seed=99, steps=5):
     """A fresh handle's rings, lists and blocks filled with OTHER bytes before it is restored over."""
     env.reset()
-    a = actions(seed, steps, env.n_envs, *((env.n_senders,) if env.n_senders > 1 else ()))
+    a = actions(seed, steps, env.n_envs, *((env.n_senders,) if env.n_senders > 1 else ()), *((2,) if env.use_cwnd else ()))
     for t in range(steps):
         env.step(a[t])
 
@@ -356,8 +356,8 @@ def test_refusals_leave_the_target_untouched():
     src.step_retire()
     src.restore(snap)   # (back to where the snapshot was taken: the comparison at the end starts there)
 
-    def refused(target, twin, how, code=-1, names=None):
-        """`how(target)` must raise; then target and twin, stepped alike, agree."""
+    def refused(target, twin, how, code=-1, names=None, width=None):
+        """`how(target)` must raise; then target and twin, stepped alike, agree (width: components per action, with use_cwnd 2)."""
         with pytest.raises((pcc_rl_amd.PccError, ValueError)) as e:
             how(target)
         if isinstance(e.value, pcc_rl_amd.PccError):
@@ -365,7 +365,7 @@ def test_refusals_leave_the_target_untouched():
         if names:
             assert names in str(e.value), str(e.value)
         m = target.n_envs
-        a = actions(14, 3, m)
+        a = actions(14, 3, m, *((width,) if width else ()))
         assert_same_steps(run(target, a, 0, 3), run(twin, a, 0, 3))
         assert_same_state(state_of(target), state_of(twin))
 
@@ -397,6 +397,30 @@ def test_refusals_leave_the_target_untouched():
     a, b = pair(n, seed=21, ring_pools=(4, 8, 32))
     refused(a, b, raw_restore, names="ring pool slots")
     a.close(); b.close()
+    # the rest of the configuration the header names (include/pcc_sim.h), one field at a time, straight through the C ABI: a
+    # target that differs from the source in the delta scale, one bound of the parameter ranges, max steps, or in having link
+    # arrays where the source has none
+    slow = ((20.0, 0.01, 0.0, 0.3, 0.1), (60.0, 0.02, 1.0, 0.9, 4.0))
+    default_but_one = ((100.0, 0.05, 0.0, 0.0, 0.3), (500.0, 0.5, 8.0, 0.0625, 1.5))   # (the loss range's upper bound: 0.05 -> 0.0625)
+    for kw, setup, field in (({"delta_scale": 0.2}, None, "delta scale"),
+                             ({}, lambda e: e.randomize_link_params(default_but_one), "parameter ranges"),
+                             ({"max_steps": 399}, None, "max steps"),
+                             ({}, lambda e: e.set_link_params(200.0, 0.03, 5.0, 0.0, 60.0), "link parameter arrays")):
+        a, b = make_env(n, seed=21, **kw), make_env(n, seed=21, **kw)
+        for e in (a, b):
+            if setup:
+                setup(e)
+            dirty(e, seed=15, steps=2)
+        refused(a, b, raw_restore, names=field)
+        a.close(); b.close()
+    # ... and the cwnd mode, on one-sender handles both ways (a window-limited target and a plain snapshot, and the reverse)
+    a, b = pair(n, seed=21, use_cwnd=True)
+    refused(a, b, raw_restore, names="cwnd mode", width=2)
+    cw_snap = a.snapshot()
+    a.close(); b.close()
+    a, b = pair(n, seed=21)
+    refused(a, b, lambda e: raw_restore(e, data=cw_snap.data), names="cwnd mode")
+    a.close(); b.close()
     a, b = pair(n, seed=21)
     refused(a, b, lambda e: raw_restore(e, nbytes=snap.nbytes - 16), names="bytes")
     refused(a, b, lambda e: raw_restore(e, nbytes=64), names="bytes")
@@ -406,6 +430,51 @@ def test_refusals_leave_the_target_untouched():
     assert_same_steps(run(a, acts, 4, 12), run(src, acts, 4, 12))
     a.close(); b.close()
     src.close()
+
+
+def test_settings_off_their_defaults_are_carried_out_of_lockstep():
+    """The positive side of the configuration check: delta_scale = 0.2 and sampling ranges of slow, lossy, shallow links (bw 20-60,
+    up to nine packets in ten lost, starting rates below MIN_RATE), masked resets that take the envs out of lockstep, a snapshot
+    with shadows prepared from those ranges; a fresh handle of the same settings continues bit for bit over every env's next
+    episode boundary (episodes of 20 steps, 30 more steps), and ends in the same state."""
+    n, seed, max_steps, cut, T = 96, 23, 20, 24, 54
+    slow = ((20.0, 0.01, 0.0, 0.3, 0.1), (60.0, 0.02, 1.0, 0.9, 4.0))
+    acts = actions(19, T, n)
+    idx = torch.arange(n)
+
+    def make():
+        env = make_env(n, seed=seed, max_steps=max_steps, delta_scale=0.2)
+        env.randomize_link_params(slow)
+        return env
+
+    def drive(env, t0, t1):
+        out = []
+        for t in range(t0, t1):
+            if t < 20 and t % 5 == 2:
+                out.append(env.reset((idx % 4) == ((t // 5) % 4)).clone())
+            o, r, d, info = env.step(acts[t])
+            out += [o.clone(), r.clone(), d.clone(), info["steps"].clone()]
+        return out
+
+    env = make()
+    env.reset()
+    drive(env, 0, cut)
+    snap = env.snapshot()
+    assert snap.config["delta_scale"] == 0.2
+    want, want_state = drive(env, cut, T), state_of(env)
+    bw = want_state["bw"]
+    assert bool(((bw >= 20.0) & (bw <= 60.0)).all()) and want_state["restart_stats"]["shadow_swaps"] > 0
+    assert bool(torch.stack(want[2::4]).any(0).all())   # (no masked reset after the cut: four entries a step; every env ended an episode)
+    env.check_flags()
+    other = make()
+    dirty(other)
+    other.restore(snap)
+    got = drive(other, cut, T)
+    assert len(got) == len(want) and all(torch.equal(x, y) for x, y in zip(want, got))
+    assert_same_state(want_state, state_of(other))
+    other.check_flags()
+    other.close()
+    env.close()
 
 
 @pytest.mark.parametrize("src_lists", [True, False])

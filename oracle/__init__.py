@@ -72,6 +72,8 @@ def lib():
         L.pcc_oracle_cur_time.argtypes = [ctypes.c_void_p]
         L.pcc_oracle_heap_len.restype = ctypes.c_long
         L.pcc_oracle_heap_len.argtypes = [ctypes.c_void_p]
+        L.pcc_oracle_in_flight.restype = ctypes.c_long
+        L.pcc_oracle_in_flight.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.pcc_oracle_link_state.restype = ctypes.c_double
         L.pcc_oracle_link_state.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.pcc_oracle_np_mean.restype = ctypes.c_double
@@ -218,7 +220,7 @@ class OracleEnv(object):
         return int(self.L.pcc_oracle_cwnd(self.h, sender))
 
     def step(self, action):
-        a = np.atleast_1d(np.asarray(action, dtype=np.float64))
+        a = np.atleast_1d(np.ascontiguousarray(action, dtype=np.float64))      # (a strided view would be read as if it were dense)
         if getattr(self, "_cwnd", False):
             a = a.reshape(self.n_senders, 2) if a.size == 2 * self.n_senders else a.reshape(1, 2)
             c = np.ascontiguousarray(a[:, 1])
@@ -247,6 +249,10 @@ class OracleEnv(object):
     @property
     def heap_len(self):
         return self.L.pcc_oracle_heap_len(self.h)
+
+    def in_flight(self, sender=0):
+        """Packets of `sender` under way: heap_len == sum of these + one pending SEND per sender."""
+        return int(self.L.pcc_oracle_in_flight(self.h, sender))
 
     @property
     def rng_draws(self):

@@ -112,6 +112,15 @@ __device__ __forceinline__ double draw_at(const DrawCtx &c, uint32_t idx, uint32
     return u32_to_unit(x == 0 ? w[0] : x == 1 ? w[1] : x == 2 ? w[2] : w[3]);
 }
 
+// Could the SENDs of a sender's interval -- t_k = nsend + k / rate < end, and the one that ends the interval -- fill its array of
+// `cap` events, n of them taken?  At most floor((end - nsend) * rate) + 2 SENDs (one more for the rounding of the additions), and
+// the sub-intervals ask for n_heap + K + 2 < cap.
+__device__ __forceinline__ bool interval_could_fill(uint32_t n, double nsend, double end, double rate, uint32_t cap) {
+    double est = nsend < end ? (end - nsend) * rate : 0.0;
+    if (!(est < 1e9)) est = 1e9;
+    return n + (uint32_t)est + 5u >= cap;
+}
+
 struct LinkState { double q, tu; };
 // the link's part of one SEND at time t with its two draws (event_engine's SEND branch, ns:155-175): the hop-1 event
 __device__ __forceinline__ void send_one(double t, double u_noise, double u_loss, double dl, double lr, double maxq, double ebw,
@@ -226,6 +235,12 @@ __global__ __launch_bounds__(T) void noise_sorted_kernel(Dev D, int warm, uint32
         }
         return;
     }
+
+    // The env's array in memory has the reference's size, and every SEND adds an event to it.  An interval whose SENDs could fill
+    // it is the event loop's, which raises the flag at the very push that does not fit -- decided here for the WHOLE interval,
+    // while nothing is written: a later sub-interval cannot hand the env over any more (it used to shorten itself to no SEND at
+    // all when the array came within three of full, and ended with PCC_FLAG_INTERNAL instead).
+    if (interval_could_fill(n_old, nsend0, end, rate, noise_cap)) return;
 
     // what the sub-intervals hand on
     uint32_t n_heap = n_old, draws = 0, sent = 0, acked = 0, lost = 0, kind = 0;
@@ -642,6 +657,10 @@ __global__ __launch_bounds__(T) void noise_sorted2_kernel(Dev D, int warm, uint3
         }
         return;
     }
+
+    // (as in the one-sender kernel: a sender's array that the interval's SENDs could fill makes the env the event loop's, decided
+    // for the whole interval while nothing is written)
+    if (interval_could_fill(n_heap[0], cur[0], end, rate[0], noise_cap) || interval_could_fill(n_heap[1], cur[1], end, rate[1], noise_cap)) return;
 
     // what the sub-intervals hand on
     uint32_t draws = 0, sent[2] = {0u, 0u}, acked[2] = {0u, 0u}, lost[2] = {0u, 0u}, kind = 3u, ksd = 0u;

@@ -177,3 +177,105 @@ def test_delta_scale_reaches_the_rate_and_the_window():
     assert o.cwnd() == 4
     o.step([0.0, 1e6])
     assert o.cwnd() == 5000
+
+
+# ---------------------------------------------------------------------------------------------------------------- latency noise
+# MAX_LATENCY_NOISE off the reference's 1.1.  The golden vectors tie both oracles to the unmodified reference at 1.1 only; at
+# 1.0 (every factor exactly 1: event times tie), 2 and 16 (packets overtake hundreds of others) the reference of
+# tests/test_noise_domain.py is that two independent restatements agree bit for bit: the C oracle here against the Python
+# oracle's heapq loop, on the Mersenne-Twister stream; the sorting models against the same Python oracle in
+# tests/test_noise_formulation.py (the links that tie at 1.0 come from there).
+from oracle.pcc_oracle_py import PyOracleEnv      # noqa: E402
+from test_noise_formulation import TIE_LINKS_1, TIE_LINKS_2, equal_time_pairs      # noqa: E402
+
+
+def c_against_python(seed, T, noise, S=1, fixed=None, cwnd=False, scale=1.0):
+    """One env of each oracle on random.Random(seed)'s stream after the constructor's 4 + S discarded draws: every step row,
+    observation, heap length and draw count.  Returns the equal-time pairs of the Python heap, summed over the steps' starts."""
+    k = 4 + S
+    c = oracle.OracleEnv(S)
+    c.rng_mt(seed, skip=k)
+    c.use_latency_noise(True, noise)
+    p = PyOracleEnv(seed=seed, n_senders=S, fixed=fixed, ctor_draws=k, use_cwnd=cwnd, latency_noise=noise)
+    if fixed is not None:
+        c.set_params(fixed[0], fixed[1], fixed[2], fixed[3], list(fixed[4:4 + S]))
+    if cwnd:
+        c.use_cwnd(True)
+    assert np.array_equal(np.asarray(c.reset()), np.asarray(p.reset()))
+    a = np.random.RandomState(seed).uniform(-1, 1.5, (T, S, 2)) * scale
+    ties = 0
+    for t in range(T):
+        ties += equal_time_pairs(p.heap)
+        act = a[t] if cwnd else (a[t, :, 0] if S > 1 else a[t, 0, 0])
+        oc, _, dc, _ = c.step(act)
+        op, _, dp, _ = p.step(act)
+        assert np.array_equal(c.last_row, np.array(p.last_rows, dtype=np.float64)), (seed, noise, t)
+        assert np.array_equal(np.asarray(oc), np.asarray(op)) and dc == dp, (seed, noise, t)
+        # a sender's packets under way are the events of its device heap: the oracle's heap holds them and one SEND per sender
+        assert c.heap_len == len(p.heap) == sum(c.in_flight(s) for s in range(S)) + S, (seed, noise, t)
+        assert [c.in_flight(s) for s in range(S)] == p.in_flight, (seed, noise, t)
+        assert c.rng_draws == p.draws, (seed, noise, t)
+    return ties
+
+
+@pytest.mark.parametrize("cwnd", [False, True])
+@pytest.mark.parametrize("n_senders", [1, 2])
+@pytest.mark.parametrize("noise", [1.0, 2.0, 16.0])
+def test_c_oracle_equals_python_oracle_off_the_reference_noise(noise, n_senders, cwnd):
+    for seed in (0, 5):
+        c_against_python(seed, 30, noise, n_senders, cwnd=cwnd)
+    c_against_python(8, 30, noise, n_senders, cwnd=cwnd, scale=8.0)
+
+
+@pytest.mark.parametrize("cwnd", [False, True])
+@pytest.mark.parametrize("fixed", TIE_LINKS_1 + TIE_LINKS_2)
+def test_c_oracle_equals_python_oracle_on_links_that_tie_at_noise_one(fixed, cwnd):
+    """Zero actions at 1.0 on the dyadic links: the ties are there (counted on the Python heap), and the C oracle's heap orders
+    them as heapq orders the reference's tuples -- (time, sender, 'A' < 'S', hop, latency, dropped)."""
+    ties = c_against_python(0, 25, 1.0, len(fixed) - 4, fixed=fixed, cwnd=cwnd, scale=0.0)
+    assert ties >= 25, ties
+
+
+class TraceRng(object):
+    """random.Random's two methods the Python oracle uses, replaying a trace (what RNG_TRACE is to the C oracle)."""
+
+    def __init__(self, u):
+        self.u, self.pos = u, 0
+
+    def random(self):
+        self.pos += 1
+        return float(self.u[self.pos - 1])
+
+    def uniform(self, a, b):
+        return a + (b - a) * self.random()
+
+
+def zero_laden_trace(n, length, seed):
+    """Uniforms of which half are exactly 0 and a quarter exactly 0.5: at MAX_LATENCY_NOISE = 2 the factors 1 and 1.5 keep the
+    event times of a dyadic link dyadic, so events tie although the noise is on -- and now the draw an event gets shows in its
+    latency, which it does not at 1.0 (every factor is 1 there whichever draw it is)."""
+    rs = np.random.RandomState(seed)
+    u = rs.random_sample((n, length))
+    pick = rs.randint(0, 4, (n, length))
+    return np.where(pick < 2, 0.0, np.where(pick == 2, 0.5, u))
+
+
+@pytest.mark.parametrize("fixed", TIE_LINKS_1 + TIE_LINKS_2)
+def test_c_oracle_equals_python_oracle_on_a_trace_whose_noise_draws_tie(fixed):
+    S, T = len(fixed) - 4, 20
+    trace = zero_laden_trace(1, 60000, 31)[0]
+    c = oracle.OracleEnv(S)
+    c.rng_trace(trace)
+    c.use_latency_noise(True, 2.0)
+    c.set_params(fixed[0], fixed[1], fixed[2], fixed[3], list(fixed[4:]))
+    p = PyOracleEnv(seed=0, n_senders=S, fixed=fixed, ctor_draws=0, latency_noise=2.0)
+    p.rng = TraceRng(trace)
+    assert np.array_equal(np.asarray(c.reset()), np.asarray(p.reset()))
+    ties = 0
+    for t in range(T):
+        ties += equal_time_pairs(p.heap)
+        act = np.zeros(S) if S > 1 else 0.0
+        c.step(act); p.step(act)
+        assert np.array_equal(c.last_row, np.array(p.last_rows, dtype=np.float64)), t
+        assert c.rng_draws == p.rng.pos < trace.size, t
+    assert ties >= 2 * T, ties

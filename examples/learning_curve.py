@@ -17,7 +17,12 @@ Evaluation: `--eval-envs` held-out envs (another seed and another range of env i
                  (the textbook TCP-like rule, computed from the env's own per-step record: a baseline, not part of the library)
 Reported per controller: mean episode return (the quantity PPO maximises, ns:194,205), loss ratio (lost / sent over the episode),
 latency ratio (mean over steps of avg latency / connection minimum, so:183-188) and link utilisation (acknowledged packets per
-second of simulated time / bandwidth)."""
+second of simulated time / bandwidth).
+
+--episode-ledger: train with PPO(track_episodes=True) -- every curve point also carries `episodes` and `true_mean_episode_return`,
+the exact mean return of the episodes finished in that iteration (the key mean_episode_return stays the proxy it was: mean step
+reward x episode length) -- and run the held-out evaluation through pcc_rl_amd.evaluate.evaluate: the per-episode accounting in
+the library's episode ledger, one call per chunk of steps, instead of six framework additions per step."""
 import argparse
 import json
 import os
@@ -28,6 +33,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pcc_rl_amd  # noqa: E402
+from pcc_rl_amd.evaluate import evaluate as ledger_evaluate  # noqa: E402
 from pcc_rl_amd.ppo import PPO  # noqa: E402
 
 COL_SENT, COL_ACKED, COL_LOST, COL_RATE, COL_TIME, COL_RUN_DUR, COL_REWARD, COL_M0 = 0, 1, 2, 3, 4, 5, 6, 7
@@ -63,6 +69,30 @@ def evaluate(name, act_fn, n, dev, seed, gid_base):
     return out
 
 
+def evaluate_with_ledger(name, act_fn, n, dev, seed, gid_base):
+    """evaluate() through the episode ledger: the same envs, the same keys.  The env resets itself after the episode, so the
+    bandwidths are read at the first step; simulated time is the episode's total of the run_dur column."""
+    env = pcc_rl_amd.BatchedNetworkEnv(n, device=dev, seed=seed, env_gid_base=gid_base)
+    seen = {"t": 0, "last": None, "bw": None}
+
+    def act(obs_row, out_row):
+        if seen["bw"] is None:
+            seen["bw"] = env.state("bw").clone()
+        out_row.copy_(act_fn(obs_row, env, seen["t"], seen["last"]).reshape(-1))
+
+    def hook(t, steps_row):
+        seen["t"], seen["last"] = t + 1, steps_row
+
+    r = ledger_evaluate(env, act, channels=("reward", "sent", "acked", "lost", "run_dur", "latency_ratio"), step_hook=hook)
+    ret, sent, acked, dur = (r["last"][:, c] for c in (1, 2, 3, 5))
+    out = {"controller": name, "envs": n, "mean_episode_return": r["channels"]["reward"]["mean"][0], "median_episode_return": float(ret.median()),
+           "loss_ratio": r["loss_ratio"][0], "mean_latency_ratio": r["mean_latency_ratio"][0],
+           "link_utilisation": float((acked / dur / seen["bw"]).mean()), "packets_per_env_step": float(sent.sum() / (n * env.max_steps)),
+           "episodes": r["episodes"][0]}
+    env.close()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=8192)
@@ -72,10 +102,13 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--normalize-obs", action="store_true",
                     help="train with PPO(normalize_obs=True); the held-out evaluation applies the trained, frozen normaliser")
+    ap.add_argument("--episode-ledger", action="store_true",
+                    help="train with PPO(track_episodes=True): true_mean_episode_return and episodes in every curve point, and the "
+                    "held-out evaluation through pcc_rl_amd.evaluate (the library's episode ledger)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device=dev, seed=args.seed)
-    agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs)
+    agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs, track_episodes=args.episode_ledger)
     untrained = {k: v.clone() for k, v in agent.policy.state_dict().items()}
     iters = max(1, int(round(args.env_steps / (args.envs * args.horizon))))
     curve = []
@@ -85,6 +118,8 @@ def main():
         curve.append({"iteration": it, "env_steps": (it + 1) * args.envs * args.horizon,
                       "mean_episode_return": s["mean_step_reward"] * env.max_steps, "mean_step_reward": s["mean_step_reward"],
                       "entropy": s.get("entropy"), "wall_s": time.perf_counter() - t0})
+        if args.episode_ledger:
+            curve[-1].update(true_mean_episode_return=s["mean_episode_return"], episodes=s["episodes"])
     train_s = time.perf_counter() - t0
     env.check_flags()
     env.close()
@@ -98,12 +133,13 @@ def main():
                 obs = agent.obs_norm.normalise(obs.contiguous())
             return pol.pi(obs).reshape(-1)
 
-    results = [evaluate("trained", policy_mean, **held)]
+    run_eval = evaluate_with_ledger if args.episode_ledger else evaluate
+    results = [run_eval("trained", policy_mean, **held)]
     trained_state = {k: v.clone() for k, v in pol.state_dict().items()}
     pol.load_state_dict(untrained)
-    results.append(evaluate("untrained", policy_mean, **held))
+    results.append(run_eval("untrained", policy_mean, **held))
     pol.load_state_dict(trained_state)
-    results.append(evaluate("fixed_rate", lambda obs, e, t, last: torch.zeros(e.n_envs, device=dev), **held))
+    results.append(run_eval("fixed_rate", lambda obs, e, t, last: torch.zeros(e.n_envs, device=dev), **held))
 
     def aimd(obs, e, t, last):
         # rate <- rate + 1 % of the starting rate, or rate / 2 after an interval with a loss; as the env's action:
@@ -116,11 +152,11 @@ def main():
             return up.to(torch.float32)
         return torch.where(last[:, COL_LOST] > 0, down, up).to(torch.float32)
 
-    results.append(evaluate("aimd", aimd, **held))
+    results.append(run_eval("aimd", aimd, **held))
     by = {r["controller"]: r for r in results}
     out = {"what": "PPO (reference hyper-parameters, pi/vf MLP 32-16) on the MI355X simulator, then the trained controller against "
                    "baselines on held-out envs; python examples/learning_curve.py",
-           "normalize_obs": bool(args.normalize_obs),
+           "normalize_obs": bool(args.normalize_obs), "episode_ledger": bool(args.episode_ledger),
            "training": {"envs": args.envs, "horizon": args.horizon, "iterations": iters, "env_steps": iters * args.envs * args.horizon,
                         "reference_budget_env_steps": 6 * 1600 * 410, "wall_s": train_s,
                         "env_steps_per_s_incl_learning": iters * args.envs * args.horizon / train_s,

@@ -11,7 +11,10 @@ PopulationPPO): seeds for a learning curve, or a sweep over learning rates, entr
 One line per iteration with every member's episode return.  --lrs / --ent-coefs / --gammas take one value or one per member.
 --pbt-every N: every N iterations the worst --pbt-frac of the members take over a good member's weights, Adam state and
 hyper-parameters, lr and ent_coef perturbed (PopulationPPO.evolve: one launch, scored by the mean reward over those N iterations);
-the line then also shows every member's parent, lr and ent_coef.  The generation travels in --checkpoint / --resume."""
+the line then also shows every member's parent, lr and ent_coef.  The generation travels in --checkpoint / --resume.
+--pbt-score episode_return: the generations are scored by the mean return of the episodes each member finished since the last
+one, counted exactly on the device (PopulationPPO(track_episodes=True): evolve() reads the episode ledger itself), and the line
+also shows every member's episodes and true mean episode return of the iteration."""
 import argparse
 import os
 import sys
@@ -21,6 +24,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pcc_rl_amd  # noqa: E402
+from pcc_rl_amd.env import MAX_STEPS  # noqa: E402
 from pcc_rl_amd.ppo import PopulationPPO  # noqa: E402
 
 
@@ -55,17 +59,25 @@ def main():
     ap.add_argument("--pbt-every", type=int, default=0, help="evolve the population every N iterations (0: never, a static sweep)")
     ap.add_argument("--pbt-frac", type=float, default=0.25, help="the share of the members replaced per generation (at most 0.5)")
     ap.add_argument("--pbt-seed", type=int, default=0)
+    ap.add_argument("--pbt-score", default="step_reward", choices=("step_reward", "episode_return"),
+                    help="what a generation selects on: the mean step reward of its iterations (default), or the mean return of the "
+                    "episodes finished in them (the episode ledger; needs --pbt-every x --horizon >= the episode length)")
     ap.add_argument("--curve", default="", help="write every iteration's returns per member -- and each generation's parents and hyper rows -- here as JSON")
     ap.add_argument("--ring-pools", default="", help="div1,div2,div3 of BatchedNetworkEnv(ring_pools=...); with --checkpoint / --resume the "
                     "default is 2,8,32 (the library's own default depends on the free device memory, and a snapshot needs equal pools): "
                     "untrained policies ran those dry at 65 536 envs (PCC_FLAG_POOL_EXHAUSTED) -- 1,2,8 held there; the same on the run that resumes")
     args = ap.parse_args()
     pools = tuple(int(x) for x in args.ring_pools.split(",")) if args.ring_pools else ((2, 8, 32) if args.checkpoint or args.resume else None)
+    ledger = args.pbt_score == "episode_return"
+    if ledger and args.pbt_every * args.horizon < MAX_STEPS:   # (said before a device is touched)
+        ap.error("--pbt-score episode_return: a generation of --pbt-every x --horizon = %d steps is shorter than an episode (%d steps): "
+                 "no member would finish one" % (args.pbt_every * args.horizon, MAX_STEPS))
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0, ring_pools=pools)
     pop = PopulationPPO(env, args.members, arch=tuple(int(x) for x in args.arch.split(",")), horizon=args.horizon,
                         lr=values(args.lrs, 1e-3), ent_coef=values(args.ent_coefs, 0.01),
                         gamma=values(args.gammas, 0.99),
-                        seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None, normalize_obs=args.normalize_obs)
+                        seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None, normalize_obs=args.normalize_obs,
+                        track_episodes=ledger)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)
@@ -90,13 +102,19 @@ def main():
         if args.pbt_every > 0:
             window.append(s["mean_step_reward"])
             if len(window) >= args.pbt_every:
-                parent, _ = pop.evolve(torch.tensor(window, dtype=torch.float64).mean(dim=0), frac=args.pbt_frac, seed=args.pbt_seed)
+                scores = None if ledger else torch.tensor(window, dtype=torch.float64).mean(dim=0)   # (None: the ledger's, on the device)
+                parent, _ = pop.evolve(scores, frac=args.pbt_frac, seed=args.pbt_seed)
                 window = []
                 curve["generations"].append({"after_iter": it, "parents": parent.tolist(), "hyper": pop.hypers()})
                 pbt = "  parents: %s  lr: %s  ent_coef: %s" % (" ".join("%d" % p for p in parent.tolist()),
                                                              " ".join("%.2e" % h[0] for h in pop.hypers()), " ".join("%.2e" % h[2] for h in pop.hypers()))
         if args.checkpoint and ((it + 1) % max(args.checkpoint_every, 1) == 0 or it + 1 == args.iters):
             checkpoint(it + 1)
+        if ledger:
+            curve.setdefault("episodes", []).append(s["episodes"])
+            curve.setdefault("true_mean_episode_return", []).append(s["mean_episode_return"])
+            pbt = "  episodes: %s  true return: %s%s" % (" ".join("%d" % e for e in s["episodes"]),
+                                                          " ".join("%7.1f" % r for r in s["mean_episode_return"]), pbt)
         steps = (it + 1 - first) * args.envs * args.horizon
         print("iter %3d  env-steps %11d  %.0f env-steps/s incl. learning  return per member: %s%s"
               % (it, steps, steps / (time.perf_counter() - t0), " ".join("%7.1f" % (r * env.max_steps) for r in s["mean_step_reward"]), pbt))

@@ -166,6 +166,51 @@ int pcc_obs_stats_update(const float *obs, int T, int64_t n_envs, int obs_dim, d
                          double *scratch, void *stream);
 int pcc_obs_normalise(const float *obs, int64_t n_envs, int obs_dim, const float *norm, float clip, float *out, void *stream);
 
+/*
+ * The episode ledger: what every episode returned -- per env the running episode and the last finished
+ * one, per member the totals of the finished episodes -- from the [T][n_envs] rows a rollout already holds.  One sender.  All
+ * buffers are caller-owned device memory; everything is enqueued on `stream`, nothing synchronizes.  Member m owns the columns
+ * [m * n_envs / n_members, (m + 1) * n_envs / n_members), as above.
+ * reward    [T][n_envs] float32; done [T][n_envs] uint8, != 0: env i's episode ended with step t
+ * steps     pcc_step_many's steps_out, [T][n_envs][PCC_STEP_COLS] float64 (include/pcc_sim.h), or NULL with n_channels == 1
+ * cols      HOST array of n_channels - 1 column indices in [0, PCC_STEP_COLS); it is read before the call returns
+ * Channels: C = n_channels, 1 <= C <= 8.  Channel 0 is (double)reward[t][i]; channel c >= 1 is steps[t][i][cols[c - 1]].  Finite
+ * rewards and columns are the contract: a NaN or an infinity is summed like any other value and spoils the episode it belongs
+ * to and the totals that episode enters (min / max then follow fmin / fmax), nothing else.
+ * carry     float64 [n_envs][C], carry_len int32 [n_envs]: every env's running episode; all zeros is the empty state
+ * last      float64 [n_envs][C], last_len int32 [n_envs]: every env's last finished episode; either may be NULL
+ * totals    float64 [n_members][totals_stride], totals_stride >= 2 + 4 C: row m is {episodes, steps, then per channel sum, sumsq,
+ *           min, max} of the channel totals of the member's finished episodes since the row was last zeroed.  All zeros is the
+ *           empty state: with episodes == 0 on entry the min / max slots are not read.  Of a member without a finished episode
+ *           in this call nothing in its row is written; the padding is never read or written.
+ * scratch   pcc_episode_scratch_doubles(n_envs, n_members, n_channels) doubles (host only; -1 outside the domain)
+ *
+ * pcc_episode_update_pop, two launches.  For every env i, for t = 0 .. T - 1 in this order: carry[i][c] += x_c, one float64
+ * addition per channel; carry_len[i] += 1; if done[t][i] != 0 the episode is finished: carry[i] / carry_len[i] go to last[i] /
+ * last_len[i] and into the member's row -- episodes += 1, steps += carry_len[i], per channel with v = carry[i][c]: sum += v,
+ * sumsq += v * v (no contraction), min, max -- and carry[i][:] = 0, carry_len[i] = 0.  So carry, carry_len, last and last_len
+ * are specified bit for bit, a call over [0, T) and two calls over [0, T1) and [T1, T) leave the same bits in the four, and
+ * with the column PCC_COL_REWARD as a channel, last reproduces the env's own last_return bit for bit.  episodes, steps, min and
+ * max are exact.  sum and sumsq add a member's episodes in a fixed order that is the implementation's: lane = env sums its own
+ * episodes in step order, a workgroup of 256 lanes its lanes in a fixed tree, one workgroup per member the workgroups' partials
+ * in index order, and the result is added to the row.
+ *
+ * No atomics, no hand-off between workgroups: the same inputs give the same bits, and a member's row, carry and last are
+ * bit-identical to the stand-alone call on a contiguous copy of its columns (a member is cut into workgroups exactly as a launch
+ * over the member alone; no divisibility is asked of the member size).  pcc_episode_update is the stand-alone form: the same
+ * kernels with one member.
+ * Returns 0; -1, with nothing written and before any device call, outside 1 <= n_channels <= 8, T >= 1, 1 <= n_members <= 1024,
+ * n_envs >= 1, n_envs % n_members == 0, totals_stride >= 2 + 4 n_channels, for a NULL reward / done / carry / carry_len / totals /
+ * scratch, a NULL steps or cols with n_channels > 1, or a column index out of range; -3 launch failure.
+ */
+int pcc_episode_scratch_doubles(int64_t n_envs, int n_members, int n_channels);
+int pcc_episode_update_pop(const float *reward, const uint8_t *done, const double *steps, const int32_t *cols, int n_channels,
+                           int T, int64_t n_envs, int n_members, double *carry, int32_t *carry_len, double *last,
+                           int32_t *last_len, double *totals, int64_t totals_stride, double *scratch, void *stream);
+int pcc_episode_update(const float *reward, const uint8_t *done, const double *steps, const int32_t *cols, int n_channels, int T,
+                       int64_t n_envs, double *carry, int32_t *carry_len, double *last, int32_t *last_len, double *totals,
+                       int64_t totals_stride, double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

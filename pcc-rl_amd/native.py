@@ -48,7 +48,8 @@ SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params",
            "pcc_get_state", "pcc_snapshot_bytes", "pcc_snapshot", "pcc_restore", "pcc_restart_stats", "pcc_fused_steps", "pcc_debug_addresses", "pcc_metric_info", "pcc_device_bytes", "pcc_debug_timeline", "pcc_debug_pass_stats",
            "pcc_policy_act", "pcc_ppo_supported", "pcc_ppo_scratch_floats", "pcc_ppo_minibatch_step", "pcc_gae",
            "pcc_policy_act_pop", "pcc_ppo_minibatch_step_pop", "pcc_gae_pop", "pcc_pbt_evolve",
-           "pcc_obs_stats_scratch_doubles", "pcc_obs_stats_update_pop", "pcc_obs_normalise_pop", "pcc_obs_stats_update", "pcc_obs_normalise"]
+           "pcc_obs_stats_scratch_doubles", "pcc_obs_stats_update_pop", "pcc_obs_normalise_pop", "pcc_obs_stats_update", "pcc_obs_normalise",
+           "pcc_episode_scratch_doubles", "pcc_episode_update_pop", "pcc_episode_update"]
 
 
 class PccError(RuntimeError):
@@ -153,6 +154,12 @@ def lib():
     L.pcc_obs_stats_update.argtypes = [vp, i32, i64, i32, vp, vp, dbl, vp, vp]
     L.pcc_obs_normalise.restype = i32
     L.pcc_obs_normalise.argtypes = [vp, i64, i32, vp, f32, vp, vp]
+    L.pcc_episode_scratch_doubles.restype = i32
+    L.pcc_episode_scratch_doubles.argtypes = [i64, i32, i32]
+    L.pcc_episode_update_pop.restype = i32
+    L.pcc_episode_update_pop.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), i32, i32, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp]
+    L.pcc_episode_update.restype = i32
+    L.pcc_episode_update.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), i32, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp]
     L.pcc_debug_pass_stats.restype = i32
     L.pcc_debug_pass_stats.argtypes = [vp, vp, i32]
     for fn in ("pcc_create", "pcc_set_link_params", "pcc_set_param_ranges", "pcc_set_rng", "pcc_set_seed",

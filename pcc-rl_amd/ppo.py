@@ -21,8 +21,9 @@ Two trainers share this module.  PPO is the single policy
 (PPO._rollout_*: the policy inside the env's launches, the double-buffered loop over a GroupedNetworkEnv's groups, the fused
 loop, the framework loop), the update the fused step or autograd.  PopulationPPO is K learners on slices of one env batch, one
 library call per stage for all of them, and evolve() between generations.  What the two have in common is written once:
-_RolloutRows (the buffers of a rollout, the observation normaliser's place in it, and the fused loop), _Trainer (the first
-observation, the checkpoint's common part) and native.call / native.current_stream.  They stay two classes: PPO draws its
+_RolloutRows (the buffers of a rollout, the observation normaliser's place in it, the fused loop, and the hand-over of the reward
+and done rows to the episode ledger of track_episodes=True: DESIGN.md section 21), _Trainer (the options, the first observation, the
+checkpoint's common part) and native.call / native.current_stream.  They stay two classes: PPO draws its
 permutations with randperm and takes the last value from the torch module, and a merge would change its numbers.
 """
 import math
@@ -32,6 +33,7 @@ from torch import nn
 
 from .env import BatchedNetworkEnv, _ptr
 from .native import call, current_stream, lib
+from .episodes import EpisodeLedger
 from .obsnorm import ObsNormalizer
 
 
@@ -241,10 +243,14 @@ class _RolloutRows(object):
             self.stepped(t)
 
     def finish(self, agent):
-        """The agent's observation for the next rollout and the normaliser's update from rows 0 .. T - 1 (what the policy saw);
-        returns the last observation row."""
+        """The agent's observation for the next rollout, the normaliser's update from rows 0 .. T - 1 (what the policy saw) and,
+        with track_episodes, the reward and done rows into the episode ledger (one library call, whichever way the rows were
+        filled); returns the last observation row."""
         T = self.T
         agent.obs = self.obs[T].clone()
+        if agent.track_episodes:
+            agent._episodes_before = agent.ledger.totals()[:, :3].clone()
+            agent.ledger.update(self.rew, self.done)
         if self.norm is not None:
             agent.raw_b, agent.raw_obs = self.dst, self.dst[T].clone()
             self.norm.update(self.dst[:T])
@@ -267,6 +273,23 @@ class _Trainer(object):
             raise ValueError("normalize_obs=True is not supported over a GroupedNetworkEnv: its groups are stepped on their own streams "
                              "and the policy reads the raw observation rows there")
 
+    def _set_episodes(self, env, track_episodes, members=1):
+        """track_episodes: an episodes.EpisodeLedger over the env batch, fed by every rollout."""
+        self.track_episodes, self.ledger = bool(track_episodes), None
+        if not self.track_episodes:
+            return
+        if env.n_senders != 1:
+            raise ValueError("track_episodes=True needs one sender per env (n_senders = %d): the ledger's rows are [T][n_envs]" % env.n_senders)
+        self.ledger = EpisodeLedger(int(env.n_envs), members, device=env.device)
+
+    def _episode_stats(self):
+        """The episodes finished in the last rollout, as the difference of the ledger's totals after and before it: per member
+        (episodes, mean return, mean length), NaN without a finished episode.  A synchronise."""
+        nan = float("nan")
+        rows = (self.ledger.totals()[:, :3] - self._episodes_before).tolist()
+        return ([int(r[0]) for r in rows], [r[2] / r[0] if r[0] > 0 else nan for r in rows],
+                [r[1] / r[0] if r[0] > 0 else nan for r in rows])
+
     def _first_obs(self, members, clip_obs, norm_eps):
         """Reset the env; with normalize_obs every member gets its own moments of its own columns (obsnorm.ObsNormalizer)."""
         self.obs = self.env.reset().clone()
@@ -288,12 +311,15 @@ class _Trainer(object):
     def _common_state(self):
         """The keys both state_dict()s end with: the observation the next rollout starts from, torch's CPU and device generator
         states (the rollout's noise and the minibatch permutations come from the device's), the env's snapshot, and with
-        normalize_obs the normaliser and the raw observation (without it the keys are what they were before the option)."""
+        normalize_obs the normaliser and the raw observation, with track_episodes the episode ledger (without an option the keys
+        are what they were before it)."""
         dev = torch.device(self.env.device)
         sd = {"obs": self.obs.detach().clone(), "torch_rng": torch.get_rng_state(),
               "device_rng": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None, "env": self.env.snapshot()}
         if self.normalize_obs:
             sd.update(normalize_obs=True, obs_norm=self.obs_norm.state_dict(), raw_obs=self.raw_obs.detach().clone())
+        if self.track_episodes:
+            sd.update(track_episodes=True, episodes=self.ledger.state_dict())
         return sd
 
     def _restore(self, sd):
@@ -304,8 +330,14 @@ class _Trainer(object):
         if theirs != self.normalize_obs:
             raise ValueError("the checkpoint was written with normalize_obs=%s, this object has normalize_obs=%s: weights without "
                              "their normaliser are meaningless" % (theirs, self.normalize_obs))
+        theirs = bool(sd.get("track_episodes", False))
+        if theirs != self.track_episodes:
+            raise ValueError("the checkpoint was written with track_episodes=%s, this object has track_episodes=%s: the running "
+                             "episodes of the env's snapshot and the ledger belong together" % (theirs, self.track_episodes))
         self.env.restore(sd["env"])
         self._load_params(sd)
+        if self.track_episodes:
+            self.ledger.load_state_dict(sd["episodes"])
         self.obs = sd["obs"].to(dev).clone()
         if self.normalize_obs:
             self.obs_norm.load_state_dict(sd["obs_norm"])
@@ -318,19 +350,22 @@ class _Trainer(object):
 class PPO(_Trainer):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
                  epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
-                 normalize_obs=False, clip_obs=10.0, norm_eps=1e-8):
+                 normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
         optimiser steps per epoch, thousands of launches of a few microseconds of work each.
         policy_in_step: collect() runs the horizon as ONE closed-loop library call per env (group) -- env.rollout, pcc_rollout:
         the policy inside the env's own launches -- with the same numbers, bit for bit, as the policy kernel + step_into loop.
         normalize_obs: the policy sees clamp((obs - mean) / sqrt(var + norm_eps), -clip_obs, clip_obs) with the running moments of
-        the raw rows (obsnorm.ObsNormalizer): frozen during a rollout, updated once at its end."""
+        the raw rows (obsnorm.ObsNormalizer): frozen during a rollout, updated once at its end.
+        track_episodes: every rollout's reward and done rows go into an episode ledger (episodes.EpisodeLedger, self.ledger) and
+        iterate() adds episodes, mean_episode_return and mean_episode_length of the episodes that rollout finished."""
         if policy_in_step and torch.device(env.device).type != "cuda":
             raise ValueError("PPO(policy_in_step=True) runs the policy inside the env's HIP launches: it needs the env on the GPU "
                              "(device=%r)" % (env.device,))
         self.policy_in_step = bool(policy_in_step)
         self._set_normalize(env, normalize_obs, policy_in_step)
+        self._set_episodes(env, track_episodes)
         self.env, self.gamma, self.lam, self.clip, self.ent_coef = env, gamma, lam, clip, ent_coef
         self.epochs, self.minibatch, self.horizon = epochs, minibatch, horizon
         torch.manual_seed(seed)
@@ -533,6 +568,9 @@ class PPO(_Trainer):
         obs_b, act_b, logp_b, adv, ret, rew = self.collect()
         stats = self.update(obs_b, act_b, logp_b, adv, ret)
         stats["mean_step_reward"] = float(rew.mean())
+        if self.track_episodes:
+            eps, ret, length = self._episode_stats()
+            stats.update(episodes=eps[0], mean_episode_return=ret[0], mean_episode_length=length[0])
         return stats
 
 
@@ -614,7 +652,7 @@ class PopulationPPO(_Trainer):
     for raises ValueError."""
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
-                 epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8):
+                 epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False):
         members = int(members)
         self._set_normalize(env, normalize_obs)
         if members < 1 or members > 1024:
@@ -632,6 +670,7 @@ class PopulationPPO(_Trainer):
         if lib().pcc_ppo_supported(int(env.obs_dim), int(arch[0]), int(arch[1])) != 1:
             raise ValueError("PopulationPPO: the library has no kernels for %d observations x hidden %s (pcc_ppo_supported)"
                              % (env.obs_dim, list(arch)))
+        self._set_episodes(env, track_episodes, members)
         self.env, self.members, self.arch = env, members, (int(arch[0]), int(arch[1]))
         self.epochs, self.horizon, self.adam_eps = epochs, horizon, 1e-5
         self.n_member = int(env.n_envs) // members
@@ -724,23 +763,33 @@ class PopulationPPO(_Trainer):
         return {"pg": [-r[0] for r in st], "vf": [0.5 * r[1] for r in st], "entropy": ent, "clip_frac": [r[2] for r in st]}
 
     def iterate(self):
-        """collect() + update(); per-member lists of mean_step_reward, pg, vf, entropy, clip_frac."""
+        """collect() + update(); per-member lists of mean_step_reward, pg, vf, entropy, clip_frac and, with track_episodes, of
+        episodes, mean_episode_return and mean_episode_length (the episodes the rollout finished; NaN without one)."""
         obs_b, act_b, logp_b, adv, ret, rew = self.collect()
         stats = self.update(obs_b, act_b, logp_b, adv, ret)
         stats["mean_step_reward"] = rew.reshape(rew.shape[0], self.members, self.n_member).mean(dim=(0, 2)).tolist()
+        if self.track_episodes:
+            stats["episodes"], stats["mean_episode_return"], stats["mean_episode_length"] = self._episode_stats()
         return stats
 
-    def evolve(self, scores, frac=0.25, factors=(0.8, 1.2), explore=("lr", "ent_coef"), bounds=None, seed=0):
+    def evolve(self, scores=None, frac=0.25, factors=(0.8, 1.2), explore=("lr", "ent_coef"), bounds=None, seed=0):
         """The step between two generations of population-based training, one launch (pcc_pbt_evolve, include/pcc_policy.h): the
         n_cut = int(frac * members) members with the lowest `scores` (K numbers or a tensor, larger is better, NaN last) each
         take over the parameters, Adam's moments and the hyper-parameters of a member drawn from the best n_cut, and the
         hyper-parameters named in `explore` are multiplied by one of the two `factors` and clamped to `bounds` ({name: (lo, hi)}).
+        scores=None (track_episodes only): the ledger's mean finished-episode return since the last such call, read on the device
+        (a member without a finished episode scores NaN: last); the ledger's totals are cleared afterwards.
         The draws are Philox's of (seed, self.generation, member): a run repeats and resumes bit for bit.  Returns (parent, rank)
         as device int32 tensors -- parent[m] == m for a member that was not replaced -- without synchronising.  The host mirror
         hyper_rows is stale from here on (None): hypers() reads the rows back."""
         if not 0.0 <= frac <= 0.5:
             raise ValueError("evolve: frac = %r (0 .. 0.5: the worst members are replaced from as many of the best)" % (frac,))
         dev = self.env.device
+        own = scores is None
+        if own:
+            if not self.track_episodes:
+                raise ValueError("evolve: scores=None takes the episode ledger's mean episode return: PopulationPPO(track_episodes=True)")
+            scores = self.ledger.scores()
         score = torch.as_tensor(scores).detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
         if score.numel() != self.members:
             raise ValueError("evolve: %d scores for %d members" % (score.numel(), self.members))
@@ -752,6 +801,10 @@ class PopulationPPO(_Trainer):
              self.generation & 0xFFFFFFFF, _ptr(parent), _ptr(rank), self._stream())
         if self.normalize_obs:   # weights without their normaliser are meaningless: a replaced member takes its parent's too
             self.obs_norm.inherit(parent)
+        if self.track_episodes:  # a replaced member's finished episodes were another policy's
+            self.ledger.inherit(parent)
+            if own:
+                self.ledger.clear()
         self.generation += 1
         self.hyper_rows = None
         return parent, rank

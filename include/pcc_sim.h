@@ -453,6 +453,51 @@ int64_t pcc_debug_timeline(pcc_sim_t *sim, uint64_t *out, int64_t n_words);
  * Synchronizes the device.  No reference counterpart. */
 int pcc_debug_pass_stats(pcc_sim_t *sim, uint64_t *out16, int reset);
 
+/* Profiling only (handles created with PCC_DEBUG_TIMELINE=2): which send path carried what, every pass kind in a slot of
+ * its own -- what the 16 slots above cannot tell apart (they count regime C with B's token scan, a team pass like a 64-lane
+ * one, reuse their slots under other meanings for two senders, and leave the lane rounds out).  A `*_PASSES` slot counts
+ * passes that committed, the `*_PACKETS` slot after it the packets they carried. */
+enum {
+    /* one sender, passes of a 64-lane wavefront (heavy_mi<.., 1>) */
+    PCC_PATH_A_PASSES = 0, PCC_PATH_A_PACKETS = 1,                 /* regime A, "always empty" */
+    PCC_PATH_B_SCAN_PASSES = 2, PCC_PATH_B_SCAN_PACKETS = 3,       /* regime B with the token scan */
+    PCC_PATH_B_FREE_PASSES = 4, PCC_PATH_B_FREE_PACKETS = 5,       /* regime B without it */
+    PCC_PATH_C_PASSES = 6, PCC_PATH_C_PACKETS = 7,                 /* regime C, the full queue astride a power of two */
+    PCC_PATH_SERIAL_PASSES = 8, PCC_PATH_SERIAL_PACKETS = 9,       /* the serial pass (accept chain or plain recurrence) */
+    /* one sender, team passes (heavy_mi<.., 4>: a workgroup per env); there is no regime C for a team, its slots stay 0 */
+    PCC_PATH_TEAM_A_PASSES = 10, PCC_PATH_TEAM_A_PACKETS = 11,
+    PCC_PATH_TEAM_B_SCAN_PASSES = 12, PCC_PATH_TEAM_B_SCAN_PACKETS = 13,
+    PCC_PATH_TEAM_B_FREE_PASSES = 14, PCC_PATH_TEAM_B_FREE_PACKETS = 15,
+    PCC_PATH_TEAM_C_PASSES = 16, PCC_PATH_TEAM_C_PACKETS = 17,
+    PCC_PATH_TEAM_SERIAL_PASSES = 18, PCC_PATH_TEAM_SERIAL_PACKETS = 19,
+    /* one sender: closed-form passes refused for the send-time preconditions / for the queue preconditions / held back
+     * after a short pass (the next stretch goes by the serial pass) / tried, but their first packet broke a precondition */
+    PCC_PATH_REFUSED_TIME = 20, PCC_PATH_REFUSED_QUEUE = 21, PCC_PATH_HELD_BACK = 22, PCC_PATH_NOTHING_COMMITTED = 23,
+    /* two senders (heavy_mi2) */
+    PCC_PATH2_TOKEN_PASSES = 24, PCC_PATH2_TOKEN_PACKETS = 25,         /* the token pass, 256 positions */
+    PCC_PATH2_SWEEP256_PASSES = 26, PCC_PATH2_SWEEP256_PACKETS = 27,   /* the 256-position sweep pass */
+    PCC_PATH2_SWEEP256_SWEEPS = 28,                                    /* ... the sweeps it spent */
+    PCC_PATH2_SWEEP64_PASSES = 29, PCC_PATH2_SWEEP64_PACKETS = 30,     /* the 64-lane chain settled side by side by sweeps */
+    PCC_PATH2_SWEEP64_SWEEPS = 31,                                     /* ... the sweeps it spent */
+    PCC_PATH2_PLAIN_PASSES = 32, PCC_PATH2_PLAIN_PACKETS = 33,         /* the plain merged recurrence */
+    PCC_PATH2_CHAIN_PASSES = 34, PCC_PATH2_CHAIN_PACKETS = 35,         /* the chain from accept to accept (builds without sweeps) */
+    /* two senders: token passes refused for the send-time / the queue preconditions, held back after a short token pass */
+    PCC_PATH2_REFUSED_TIME = 36, PCC_PATH2_REFUSED_QUEUE = 37, PCC_PATH2_HELD_BACK = 38,
+    /* one or two senders */
+    PCC_PATH_LANE_ROUND_PACKETS = 40,   /* packets sent by the lane rounds of the light items */
+    PCC_PATH_ENVS_HEAVY = 41,           /* env intervals sent whole by a wavefront (heavy items) */
+    PCC_PATH_ENVS_TEAM = 42,            /* ... by a workgroup (team items) */
+    PCC_PATH_ENVS_TAKEN_OVER = 43,      /* ... begun by lane rounds and finished by the wave path */
+    /* ... of PCC_PATH_LANE_ROUND_PACKETS, those of launches that walk the work lists: the knobs that choose a path by the
+     * predicted packets (heavy_predict, team_predict) act through the lists, and the step after a reset, the warm-up intervals
+     * and small batches run without them -- every env by lane rounds, in index order, whatever the knobs say */
+    PCC_PATH_LANE_ROUND_LISTED_PACKETS = 44,
+    PCC_PATH_SLOTS = 48                 /* slots 39 and 45..47 are not used */
+};
+/* Copies the PCC_PATH_SLOTS counters since creation or the last reset into out (n_slots >= PCC_PATH_SLOTS).
+ * Synchronizes the device.  No reference counterpart. */
+int pcc_debug_path_stats(pcc_sim_t *sim, uint64_t *out, int n_slots, int reset);
+
 #ifdef __cplusplus
 }
 #endif

@@ -254,6 +254,10 @@ constexpr bool kProfile = PCC_PROFILE != 0;
 __device__ __forceinline__ bool prof_on(const Dev &D) { return kProfile && D.timeline != nullptr; }
 __device__ __forceinline__ bool prof_counters(const Dev &D) { return kProfile && D.pass_counters != 0; }
 __device__ __forceinline__ bool prof_skip(const Dev &D, int bit) { return kProfile && (D.debug_skip & bit) != 0; }
+// the per-path counters (PCC_PATH_* of pcc_sim.h) follow the 16 pass counters in the same block; one lane of the wavefront calls
+__device__ __forceinline__ void path_count(const Dev &D, int slot, unsigned long long n) {
+    if (prof_counters(D)) atomicAdd(&D.pass_stats[16 + slot], n);
+}
 
 // --------------------------------------------------------------------------------------
 // small helpers

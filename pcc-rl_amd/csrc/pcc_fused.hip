@@ -84,6 +84,7 @@ __device__ __forceinline__ void fused_light_loop(const Dev &D, SendLds<NS, 4> &l
         const bool prio = t < D.prio_light_items;   // (the longest light items are the launch's critical path)
         if (prio) set_prio(D.prio_level);
         const uint64_t left = send_light_item<NS, TRACE>(D, lane, i, has, tl_base + t, 0, 0u, actions, actions_f64, pk);
+        if (prof_counters(D) && lane == 0) path_count(D, PCC_PATH_LANE_ROUND_LISTED_PACKETS, (unsigned long long)pk);
         const uint64_t live = __ballot(has);
         fused_drain();
         fused_push(D, read_buf, xcc, 0u, live & ~left, lane, i);

@@ -98,6 +98,7 @@ __device__ __forceinline__ void light_body(const Dev &D, LDS &lds, const uint32_
         if (prio) set_prio(D.prio_level);
         uint32_t pk = 0;
         const uint64_t left = send_light_item<NS, TRACE>(D, lane, i, has, tl_base + t, warm, warm_mi, actions, actions_f64, pk);
+        if (prof_counters(D) && listed && lane == 0) path_count(D, PCC_PATH_LANE_ROUND_LISTED_PACKETS, (unsigned long long)pk);
         if (left) {
             // the item's last lanes (see send_light_item) go on by the wave path, from the state the item just stored: what
             // one lane wrote is read by others of this wavefront -- a workgroup-scope fence orders that (same L1)

@@ -539,6 +539,8 @@ __device__ __forceinline__ uint64_t send_light_item(const Dev &D, const uint32_t
     for (int s = 0; s < NS; s++) pk += E.live ? E.sent[s] : 0u;
     for (int o = 32; o; o >>= 1) pk += (uint32_t)__shfl_xor((int)pk, o);
     packets_out = pk;
+    if (prof_counters(D) && lane == (uint32_t)__ffsll((unsigned long long)__ballot(true)) - 1u)
+        path_count(D, PCC_PATH_LANE_ROUND_PACKETS, (unsigned long long)pk);
     return __ballot(active);
 }
 
@@ -631,6 +633,8 @@ __device__ __forceinline__ uint32_t send_wave_item(const Dev &D, const uint32_t 
             for (int s = 0; s < NS; s++) before += sent_new[s];
             if (lane == 0) slots[k].cost0 = (uint32_t)wall_clock64();   // (SndBlk::send_cost; const_cast-free: the slot is this wavefront's)
             if (bits & 2u) {
+                if (prof_counters(D) && lane == 0 && writer)   // (profile build: who sends this env's interval)
+                    path_count(D, !fresh ? PCC_PATH_ENVS_TAKEN_OVER : W > 1 ? PCC_PATH_ENVS_TEAM : PCC_PATH_ENVS_HEAVY, 1ull);
                 if constexpr (NS == 1) {
                     SendState st;
                     if (prof_counters(D) && lane == 0 && writer) atomicAdd(&D.pass_stats[fresh ? 11 : 12], 1ull);

@@ -20,6 +20,7 @@ const double h_metric_max[PCC_N_METRICS] = {1e9, 1e9, 100.0, 100.0, 100.0, 1.0, 
 const double h_metric_scale[PCC_N_METRICS] = {1e7, 1e7, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0, 1.0};
 
 thread_local char g_err[512] = "";
+constexpr int kStatSlots = 16 + PCC_PATH_SLOTS;   // profile build: pcc_debug_pass_stats' counters, then pcc_debug_path_stats'
 
 int fail(int code, const char *fmt, ...) {
     va_list ap;
@@ -45,6 +46,7 @@ struct pcc_sim {
     size_t tier_bytes[kMaxTiers];
     size_t ring_bytes;
     void *timeline_blob;
+    void *stats_blob;   // profile build: the 16 pass counters and the PCC_PATH_SLOTS path counters behind them (kStatSlots words)
     bool ever_reset;
     bool lockstep;      // every env was last reset by the same full reset (host knows when `done` fires)
     uint32_t host_steps;
@@ -744,13 +746,18 @@ int pcc_create(int64_t n_envs, int n_senders, int history_len, const int32_t *fe
         return fail(PCC_EHIP, "initialising the env state failed");
     }
     if (kProfile && getenv("PCC_DEBUG_TIMELINE") && atoi(getenv("PCC_DEBUG_TIMELINE"))) {  // profile build only
-        const size_t timeline_bytes = (size_t)n_envs * 4 * 8 * sizeof(uint64_t);
-        if (hipMalloc(&sim->timeline_blob, timeline_bytes) != hipSuccess || hipMemset(sim->timeline_blob, 0, timeline_bytes) != hipSuccess) {
+        // (32 words per env; the retire workgroups' rows start at word 16 n, (n + 7) / 8 + 1 of them: 64 words more hold them for n < 2)
+        const size_t timeline_bytes = ((size_t)n_envs * 4 * 8 + 64) * sizeof(uint64_t);
+        // the counters have a block of their own, of a size that does not depend on n_envs (they used to sit at word 24 n of the
+        // timeline's 32 n: outside it for a batch of one env)
+        const size_t stats_bytes = (size_t)kStatSlots * sizeof(uint64_t);
+        if (hipMalloc(&sim->timeline_blob, timeline_bytes) != hipSuccess || hipMemset(sim->timeline_blob, 0, timeline_bytes) != hipSuccess ||
+            hipMalloc(&sim->stats_blob, stats_bytes) != hipSuccess || hipMemset(sim->stats_blob, 0, stats_bytes) != hipSuccess) {
             pcc_destroy(sim);
             return fail(PCC_ENOMEM, "hipMalloc for the debug timeline failed");
         }
         d.timeline = static_cast<uint64_t *>(sim->timeline_blob);
-        d.pass_stats = reinterpret_cast<unsigned long long *>(d.timeline + (size_t)n_envs * 24);  // past everything the timeline uses
+        d.pass_stats = static_cast<unsigned long long *>(sim->stats_blob);
         d.pass_counters = atoi(getenv("PCC_DEBUG_TIMELINE")) >= 2;
     }
     // the send half's work lists: two buffers of kClasses lists, each able to hold every env
@@ -822,6 +829,20 @@ int pcc_debug_pass_stats(pcc_sim_t *sim, uint64_t *out16, int reset) {
     return PCC_OK;
 }
 
+int pcc_debug_path_stats(pcc_sim_t *sim, uint64_t *out, int n_slots, int reset) {
+    if (!sim || !out) return fail(PCC_EINVAL, "NULL argument");
+    if (n_slots < PCC_PATH_SLOTS) return fail(PCC_EINVAL, "pcc_debug_path_stats needs room for %d slots", (int)PCC_PATH_SLOTS);
+    if (!sim->d.pass_stats || !sim->d.pass_counters)
+        return fail(PCC_ESTATE, "path statistics are off (create the handle with PCC_DEBUG_TIMELINE=2)");
+    DeviceGuard guard(sim->device);
+    unsigned long long *src = sim->d.pass_stats + 16;
+    if (hipDeviceSynchronize() != hipSuccess ||
+        hipMemcpy(out, src, PCC_PATH_SLOTS * sizeof(uint64_t), hipMemcpyDeviceToHost) != hipSuccess ||
+        (reset && hipMemset(src, 0, PCC_PATH_SLOTS * sizeof(uint64_t)) != hipSuccess))
+        return fail(PCC_EHIP, "reading the path statistics failed");
+    return PCC_OK;
+}
+
 void pcc_destroy(pcc_sim_t *sim) {
     if (!sim) return;
     DeviceGuard guard(sim->device);
@@ -832,6 +853,7 @@ void pcc_destroy(pcc_sim_t *sim) {
         if (*e) (void)hipEventDestroy(*e);
     if (sim->shadow_blob) (void)hipFree(sim->shadow_blob);
     if (sim->timeline_blob) (void)hipFree(sim->timeline_blob);
+    if (sim->stats_blob) (void)hipFree(sim->stats_blob);
     if (sim->list_blob) (void)hipFree(sim->list_blob);
     if (sim->noise_blob) (void)hipFree(sim->noise_blob);
     if (sim->noise_out_blob) (void)hipFree(sim->noise_out_blob);

@@ -582,6 +582,11 @@ __device__ __forceinline__ void heavy_mi(const Dev &D, uint32_t lane, const uint
                     atomicAdd(&D.pass_stats[c], 1ull);
                     atomicAdd(&D.pass_stats[4 + c], (unsigned long long)ncommit);
                     atomicAdd(&D.pass_stats[13], (unsigned long long)(__builtin_readcyclecounter() - dbg_c0));
+                    // ... and by regime and by who sent it (PCC_PATH_*: A, B with the scan, B without, C; a wavefront or a team)
+                    const int p = (W > 1 ? PCC_PATH_TEAM_A_PASSES : PCC_PATH_A_PASSES) +
+                                  (regime == 1 ? 0 : regime == 3 ? 6 : (!free_mode && Gi < Ri) ? 2 : 4);
+                    path_count(D, p, 1ull);
+                    path_count(D, p + 1, (unsigned long long)ncommit);
                 }
                 st.t = (t0 + (double)(ncommit - 1u) * G) + gap;  // ns:161 on the last packet's (exact) send time
                 st.a += j_stop;
@@ -591,9 +596,13 @@ __device__ __forceinline__ void heavy_mi(const Dev &D, uint32_t lane, const uint
                 serial_len = 8;
                 continue;
             }
-            if (prof_counters(D) && lane == 0 && writer) atomicAdd(&D.pass_stats[8], 1ull);  // nothing to commit: first packet flagged
+            if (prof_counters(D) && lane == 0 && writer) {  // nothing to commit: first packet flagged
+                atomicAdd(&D.pass_stats[8], 1ull);
+                path_count(D, PCC_PATH_NOTHING_COMMITTED, 1ull);
+            }
         } else if (prof_counters(D) && lane == 0 && writer) {
             atomicAdd(&D.pass_stats[ok_t ? 10 : 9], 1ull);
+            path_count(D, !ok_t ? PCC_PATH_REFUSED_TIME : chain_left ? PCC_PATH_HELD_BACK : PCC_PATH_REFUSED_QUEUE, 1ull);
         }
         // ---- serial pass: up to serial_len packets with the plain recurrence, wave-uniform (every lane
         // computes the same values; lane k keeps packet k's record), exact with no precondition
@@ -711,6 +720,8 @@ __device__ __forceinline__ void heavy_mi(const Dev &D, uint32_t lane, const uint
                 atomicAdd(&D.pass_stats[3], 1ull);
                 atomicAdd(&D.pass_stats[7], (unsigned long long)nv);
                 atomicAdd(&D.pass_stats[14], (unsigned long long)(__builtin_readcyclecounter() - dbg_c0));
+                path_count(D, W > 1 ? PCC_PATH_TEAM_SERIAL_PASSES : PCC_PATH_SERIAL_PASSES, 1ull);
+                path_count(D, W > 1 ? PCC_PATH_TEAM_SERIAL_PACKETS : PCC_PATH_SERIAL_PACKETS, (unsigned long long)nv);
             }
         }
     }
@@ -776,6 +787,8 @@ __device__ __forceinline__ void heavy_mi2(const Dev &D, uint32_t lane, double dl
             // (the conditions above) -- not exact drains, not the queue in one binade.  Taken for the passes after a token
             // pass that stopped early, and whenever the token pass is refused.
             const bool oks = kRelaxSweeps != 0 && okb;
+            bool dbg_ok_t = false, dbg_held = false;   // (profile build: why a token pass is refused, PCC_PATH2_*)
+            if (kProfile) { dbg_ok_t = okb; dbg_held = chain_left != 0u; }
             okb = okb && (st.tu + st.tu >= tend_max) && chain_left == 0u && (st.q > 0.0) && e > 64u && e < 1100u && (x0 > 0.0) && eb <= e &&
                   exponent_bits(st.tu) >= e && exponent_bits(maxq) >= e;
             if (chain_left) chain_left--;
@@ -820,6 +833,8 @@ __device__ __forceinline__ void heavy_mi2(const Dev &D, uint32_t lane, double dl
                 }
             }
             if (kProfile && !okb && !(st.prof_why & 0x3FFu)) st.prof_why |= 1024u;   // (the grid of u: a tie on odd multiples, a span too wide)
+            if (prof_counters(D) && lane == 0 && !okb)
+                path_count(D, !dbg_ok_t ? PCC_PATH2_REFUSED_TIME : dbg_held ? PCC_PATH2_HELD_BACK : PCC_PATH2_REFUSED_QUEUE, 1ull);
             if (okb || oks) {
                 const uint32_t sent_all = st.sent[0] + st.sent[1];
                 const uint32_t skip = sent_all & 3u;   // positions of lane 0's Philox block that were sent before this pass
@@ -980,6 +995,15 @@ __device__ __forceinline__ void heavy_mi2(const Dev &D, uint32_t lane, double dl
                     atomicAdd(&D.pass_stats[6], (unsigned long long)ncommit);
                     atomicAdd(&D.pass_stats[8], (unsigned long long)dbg_sweeps256);
                     atomicAdd(&D.pass_stats[14], (unsigned long long)(__builtin_readcyclecounter() - dbg_c0));
+                    path_count(D, PCC_PATH2_SWEEP256_SWEEPS, (unsigned long long)dbg_sweeps256);   // (also of a pass that commits nothing)
+                    if (ncommit) {
+                        path_count(D, PCC_PATH2_SWEEP256_PASSES, 1ull);
+                        path_count(D, PCC_PATH2_SWEEP256_PACKETS, (unsigned long long)ncommit);
+                    }
+                }
+                if (prof_counters(D) && lane == 0 && okb && ncommit) {
+                    path_count(D, PCC_PATH2_TOKEN_PASSES, 1ull);
+                    path_count(D, PCC_PATH2_TOKEN_PACKETS, (unsigned long long)ncommit);
                 }
                 if (prof_counters(D) && lane == 0 && okb) {   // (profile build: token passes / their packets / their cycles)
                     atomicAdd(&D.pass_stats[1], 1ull);
@@ -1267,6 +1291,10 @@ __device__ __forceinline__ void heavy_mi2(const Dev &D, uint32_t lane, double dl
             atomicAdd(&D.pass_stats[4 + c], (unsigned long long)nv);
             atomicAdd(&D.pass_stats[ok ? 14 : 9], (unsigned long long)(__builtin_readcyclecounter() - dbg_c1));
             if (dbg_settled) atomicAdd(&D.pass_stats[8], (unsigned long long)dbg_sweeps);
+            const int p = !ok ? PCC_PATH2_PLAIN_PASSES : dbg_settled ? PCC_PATH2_SWEEP64_PASSES : PCC_PATH2_CHAIN_PASSES;
+            path_count(D, p, 1ull);
+            path_count(D, p + 1, (unsigned long long)nv);
+            if (dbg_settled) path_count(D, PCC_PATH2_SWEEP64_SWEEPS, (unsigned long long)dbg_sweeps);
         }
     }
 }

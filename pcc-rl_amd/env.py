@@ -521,6 +521,26 @@ class BatchedNetworkEnv(object):
         check(self._L.pcc_debug_pass_stats(self._h, out.ctypes.data, 1 if reset else 0))
         return dict(zip(self.PASS_STAT_NAMES, [int(v) for v in out]))
 
+    # slot -> name of the PCC_PATH_* enum of include/pcc_sim.h, lower-cased (None: a slot the enum leaves out);
+    # tests/test_abi_cpu.py holds the two against each other
+    PATH_STAT_NAMES = ("a_passes", "a_packets", "b_scan_passes", "b_scan_packets", "b_free_passes", "b_free_packets",
+                       "c_passes", "c_packets", "serial_passes", "serial_packets",
+                       "team_a_passes", "team_a_packets", "team_b_scan_passes", "team_b_scan_packets", "team_b_free_passes",
+                       "team_b_free_packets", "team_c_passes", "team_c_packets", "team_serial_passes", "team_serial_packets",
+                       "refused_time", "refused_queue", "held_back", "nothing_committed",
+                       "two_token_passes", "two_token_packets", "two_sweep256_passes", "two_sweep256_packets", "two_sweep256_sweeps",
+                       "two_sweep64_passes", "two_sweep64_packets", "two_sweep64_sweeps", "two_plain_passes", "two_plain_packets",
+                       "two_chain_passes", "two_chain_packets", "two_refused_time", "two_refused_queue", "two_held_back", None,
+                       "lane_round_packets", "envs_heavy", "envs_team", "envs_taken_over", "lane_round_listed_packets",
+                       None, None, None)
+
+    def debug_path_stats(self, reset=True):
+        """Which send path carried what (PCC_DEBUG_TIMELINE=2 at creation; pcc_debug_path_stats in include/pcc_sim.h), as a dict."""
+        import numpy as np
+        out = np.zeros(len(self.PATH_STAT_NAMES), dtype=np.uint64)
+        check(self._L.pcc_debug_path_stats(self._h, out.ctypes.data, len(out), 1 if reset else 0))
+        return {k: int(v) for k, v in zip(self.PATH_STAT_NAMES, out) if k}
+
     def close(self):
         h, self._h = getattr(self, "_h", None), None
         if h:

@@ -45,7 +45,7 @@ TUNE = {
 SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params", "pcc_set_param_ranges",
            "pcc_set_rng", "pcc_set_seed", "pcc_set_tuning", "pcc_set_ring_pools", "pcc_set_cwnd_mode", "pcc_set_latency_noise", "pcc_set_delta_scale", "pcc_set_max_steps", "pcc_reset", "pcc_step", "pcc_step_many", "pcc_rollout", "pcc_step_send",
            "pcc_step_retire",
-           "pcc_get_state", "pcc_snapshot_bytes", "pcc_snapshot", "pcc_restore", "pcc_restart_stats", "pcc_fused_steps", "pcc_debug_addresses", "pcc_metric_info", "pcc_device_bytes", "pcc_debug_timeline", "pcc_debug_pass_stats",
+           "pcc_get_state", "pcc_snapshot_bytes", "pcc_snapshot", "pcc_restore", "pcc_restart_stats", "pcc_fused_steps", "pcc_debug_addresses", "pcc_metric_info", "pcc_device_bytes", "pcc_debug_timeline", "pcc_debug_pass_stats", "pcc_debug_path_stats",
            "pcc_policy_act", "pcc_ppo_supported", "pcc_ppo_scratch_floats", "pcc_ppo_minibatch_step", "pcc_gae",
            "pcc_policy_act_pop", "pcc_ppo_minibatch_step_pop", "pcc_gae_pop", "pcc_pbt_evolve",
            "pcc_obs_stats_scratch_doubles", "pcc_obs_stats_update_pop", "pcc_obs_normalise_pop", "pcc_obs_stats_update", "pcc_obs_normalise",
@@ -162,6 +162,8 @@ def lib():
     L.pcc_episode_update.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), i32, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp]
     L.pcc_debug_pass_stats.restype = i32
     L.pcc_debug_pass_stats.argtypes = [vp, vp, i32]
+    L.pcc_debug_path_stats.restype = i32
+    L.pcc_debug_path_stats.argtypes = [vp, vp, i32, i32]
     for fn in ("pcc_create", "pcc_set_link_params", "pcc_set_param_ranges", "pcc_set_rng", "pcc_set_seed",
                "pcc_set_delta_scale", "pcc_set_max_steps", "pcc_reset", "pcc_step", "pcc_step_many", "pcc_rollout", "pcc_step_send",
                "pcc_step_retire", "pcc_get_state", "pcc_metric_info"):

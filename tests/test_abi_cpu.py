@@ -47,6 +47,24 @@ def test_header_and_binding_agree():
     assert keys == native.TUNE
 
 
+def test_path_counter_slots_agree():
+    """The PCC_PATH_* / PCC_PATH2_* enum of pcc_sim.h (what the profile build's kernels count into, pcc_debug_path_stats) against
+    the names the binding gives the slots: every slot of the enum has its name at its number, slots the enum leaves out have
+    none, no number is used twice, and the binding asks for exactly PCC_PATH_SLOTS slots."""
+    from pcc_rl_amd.env import BatchedNetworkEnv
+    text = open(os.path.join(ROOT, "include", "pcc_sim.h")).read()
+    found = re.findall(r"\bPCC_PATH(2?)_([A-Z0-9_]+)\s*=\s*(\d+)", text)
+    slots = {int(n): ("two_" if two else "") + name.lower() for two, name, n in found if name != "SLOTS"}
+    n_slots = [int(n) for _, name, n in found if name == "SLOTS"]
+    assert len(found) == len(slots) + 1 and n_slots == [48]                       # (no number twice; the parse found the enum)
+    names = BatchedNetworkEnv.PATH_STAT_NAMES
+    assert len(names) == n_slots[0] and max(slots) < n_slots[0]
+    assert {i: n for i, n in enumerate(names) if n is not None} == slots
+    assert len(set(slots.values())) == len(slots) >= 40
+    assert "pcc_debug_path_stats" in native.SYMBOLS and "pcc_debug_pass_stats" in native.SYMBOLS
+    assert len(BatchedNetworkEnv.PASS_STAT_NAMES) == 16                           # (the older export keeps its 16 slots)
+
+
 def test_library_exports_every_declared_symbol(libpath):
     L = ctypes.CDLL(libpath)
     for name in declared_functions():

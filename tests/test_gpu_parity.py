@@ -37,6 +37,26 @@ def run_gpu(env, actions, n_steps):
             torch.stack(dones, 1).cpu().numpy())
 
 
+def _reach(env, label=""):
+    """For tests/test_path_reach.py, which runs this file on the profile build to see which send path carried each case:
+    appends one JSON line -- the running test's id, `label` (the knob set or the golden), the handle's path counters and
+    the packets its envs sent -- to the file PCC_REACH_OUT names.  Does nothing when the variable is not set."""
+    out = os.environ.get("PCC_REACH_OUT")
+    if not out:
+        return
+    import json
+    test = os.environ.get("PYTEST_CURRENT_TEST", "").split(" ")[0].split("::")[-1]
+    rec = {"test": test, "label": label, "n_envs": env.n_envs, "n_senders": env.n_senders,
+           "total_sent": int(env.state("total_sent").sum().item()),
+           "path": env.debug_path_stats(reset=False), "pass": env.debug_pass_stats(reset=False)}
+    with open(out, "a") as f:
+        f.write(json.dumps(rec, sort_keys=True) + "\n")
+
+
+def _knobs(knobs):
+    return ", ".join("%s=%g" % kv for kv in knobs.items()) or "defaults"
+
+
 def golden_env(d, history_len=10, features=None, n_senders=1):
     """Batch of the golden cases in trace mode: parameters from the fixture, loss uniforms =
     the MT19937 stream random.Random(seed) continues with after the parameter draws."""
@@ -154,6 +174,7 @@ def test_philox_batches_with_odd_shapes_match_oracle(n_envs, n_steps, seed, n_se
     assert np.array_equal(steps, ref["steps"])
     assert np.array_equal(obs, ref["obs"].astype(np.float32))
     env.check_flags()
+    _reach(env)
     env.close()
 
 
@@ -320,8 +341,10 @@ def test_old_gym_adapter_drop_in():
     dict(send_waves=32, heavy_predict=64.0),                     # more wavefronts than items
     dict(send_envs_per_wave=64, heavy_predict=256.0, takeover_lanes=8),
     dict(heavy_predict=16.0, round_packets=16),                  # nearly everything by wave passes of every regime
-    dict(heavy_predict=0.0, team_predict=0.0),                   # every env a TEAM item: four wavefronts, 1 024 positions per pass
-    dict(heavy_predict=16.0, team_predict=100.0, round_packets=16),   # lane rounds, wave passes and team passes side by side
+    # every env a TEAM item: four wavefronts, 1 024 positions per pass (no lane handed to a lone wavefront in the list-less first step)
+    dict(heavy_predict=0.0, team_predict=0.0, takeover_lanes=0),
+    # lane rounds, wave passes and team passes side by side, about a third of the packets each (tests/test_path_reach.py)
+    dict(heavy_predict=470.0, team_predict=1800.0, round_packets=16),
     dict(team_predict=1e18),                                     # no team items: the giants on one wavefront
     dict(heavy_predict=64.0, team_predict=64.0, send_waves=1),   # more team items than team workgroups
     dict(retire_wide_predict=0.0),                               # retire half: every env by 16 lanes
@@ -344,12 +367,13 @@ def test_send_paths_are_exact_whatever_the_tuning(knobs):
     assert np.array_equal(steps[..., :3], ref["steps"][..., :3])
     assert np.array_equal(steps, ref["steps"])
     assert np.array_equal(obs, ref["obs"].astype(np.float32))
+    _reach(env, _knobs(knobs))
     env.close()
 
 
 @pytest.mark.parametrize("knobs", [
     dict(),                                              # defaults: rounds, then the two-sender wave path
-    dict(takeover_lanes=0),                              # lane-serial only
+    dict(takeover_lanes=0, heavy_predict=1e18),          # lane-serial only (without heavy_predict most packets went by heavy items)
     dict(takeover_lanes=64, round_packets=8),            # merge-path wave passes for almost everything
     dict(takeover_lanes=64, round_packets=4, heavy_predict=200.0),
     dict(heavy_predict=100.0, send_waves=2),
@@ -372,6 +396,7 @@ def test_two_sender_philox_batches_match_oracle(knobs):
     assert bad.size == 0, "envs with count mismatches: %s" % bad[:10].ravel()
     assert np.array_equal(steps, ref["steps"])
     assert np.array_equal(obs, ref["obs"].astype(np.float32))
+    _reach(env, _knobs(knobs))
     env.close()
 
 
@@ -390,6 +415,7 @@ def test_two_sender_wave_path_across_powers_of_two_in_time_matches_oracle():
     ref = oracle.run_batch(acts, n_senders=2, rng_mode=oracle.RNG_PHILOX, seed=seed)
     assert np.array_equal(steps, ref["steps"])
     assert np.array_equal(obs, ref["obs"].astype(np.float32))
+    _reach(env)
     env.close()
 
 
@@ -403,6 +429,7 @@ def test_two_sender_wave_path_on_golden_trace():
     T = d["actions"].shape[1]
     steps, obs, _ = run_gpu(env, d["actions"], T)
     assert np.array_equal(steps, d["steps"])
+    _reach(env)
     env.close()
 
 
@@ -412,24 +439,27 @@ def test_wave_path_on_golden_traces():
     for name in ("saturating_0_2", "fixed_deepq", "fixed_lossy"):
         d = load(name)
         env = golden_env(d, history_len=int(d["history_len"]))
-        env.set_tuning(heavy_predict=0.0)
+        env.set_tuning(heavy_predict=0.0, team_predict=1e18)
         env.reset()
-        env.set_tuning(heavy_predict=0.0, takeover_lanes=64, round_packets=4)
+        env.set_tuning(heavy_predict=0.0, team_predict=1e18, takeover_lanes=64, round_packets=4)   # (team_predict: no env to a workgroup)
         steps, obs, done = run_gpu(env, d["actions"], d["actions"].shape[1])
         assert np.array_equal(steps, d["steps"]), name
+        _reach(env, name)
         env.close()
 
 
 def test_team_path_on_golden_traces():
     """Trace mode through the team path (a whole workgroup per env, heavy_mi<.., 4>): the reference's own episodes with
-    every env a team item from its first interval on."""
+    every env a team item from its second interval on (the step after a reset has no work lists: lane rounds)."""
     for name in ("saturating_0_2", "fixed_deepq", "fixed_lossy", "default_pm1"):
         d = load(name)
         env = golden_env(d, history_len=int(d["history_len"]))
+        env.set_tuning(takeover_lanes=0)   # (no lane of the list-less steps -- the reset's warm-up intervals, the first step -- to a lone wavefront)
         env.reset()
-        env.set_tuning(heavy_predict=0.0, team_predict=0.0)
+        env.set_tuning(heavy_predict=0.0, team_predict=0.0, takeover_lanes=0)
         steps, obs, done = run_gpu(env, d["actions"], d["actions"].shape[1])
         assert np.array_equal(steps, d["steps"]), name
+        _reach(env, name)
         env.close()
 
 
@@ -482,6 +512,7 @@ def test_edge_links_match_oracle(params, feats, hist):
     assert np.array_equal(obs0, ref["obs0"].astype(np.float32))
     assert np.array_equal(steps, ref["steps"])
     assert np.array_equal(obs, ref["obs"].astype(np.float32))
+    _reach(env)
     env.close()
 
 
@@ -510,6 +541,7 @@ def test_long_drop_runs_match_oracle(params, wide):
     assert steps[..., 2].sum() > 5 * steps[..., 1].sum() or params[0] > 200, "the links are meant to lose most of their packets"
     assert np.array_equal(steps, ref["steps"])
     assert np.array_equal(obs, ref["obs"].astype(np.float32))
+    _reach(env)
     env.close()
 
 
@@ -1154,7 +1186,8 @@ def test_grouped_env_is_the_same_envs_on_several_streams():
 def test_queue_limits_just_above_a_power_of_two_match_oracle():
     """Regime C of the wave passes: envs whose queue limit sits just above a power of two (0.25 .. 16 s) and whose sender
     overdrives the link -- the full queue straddles the power of two, fl(qcur + 1/bw) rounds on two grids -- against the
-    oracle, every column; half of them sent one env per wavefront from the first interval on."""
+    oracle, every column; half of them sent one env per wavefront from the second interval on (the step after a reset
+    has no work lists: its interval goes by lane rounds whatever the knobs say)."""
     n_envs, n_steps, seed = 512, 160, 41
     rs = np.random.RandomState(seed)
     bw = rs.uniform(100, 500, n_envs)
@@ -1174,6 +1207,7 @@ def test_queue_limits_just_above_a_power_of_two_match_oracle():
         assert np.array_equal(steps[..., :3], ref["steps"][..., :3]), knobs
         assert np.array_equal(steps, ref["steps"]), knobs
         assert np.array_equal(obs, ref["obs"].astype(np.float32)), knobs
+        _reach(env, _knobs(knobs))
         env.close()
 
 
@@ -1181,7 +1215,7 @@ def test_queue_limits_just_above_a_power_of_two_match_oracle():
 def test_two_sender_token_pass_matches_oracle(case):
     """The closed-form pass of the two-sender wave path (heavy_mi2: backlogged queue in one binade, accept decisions by a
     token scan over the merged stream with uneven token arrivals) against the oracle, every env sent by the wave path
-    from its first packet: two senders that together overdrive the link (the pass's home ground), queue limits around
+    (from its second interval on, or from its ninth packet): two senders that together overdrive the link (the pass's home ground), queue limits around
     powers of two and 1/bw on both sides of the queue's binade (its preconditions break and hold by turns), and the
     default parameter ranges."""
     n_envs, n_steps, seed = 768, 120, {"overdriven": 61, "edges": 62, "mixed": 63}[case]
@@ -1210,6 +1244,7 @@ def test_two_sender_token_pass_matches_oracle(case):
         assert bad.size == 0, (knobs, "envs with count mismatches: %s" % bad[:10].ravel())
         assert np.array_equal(steps, ref["steps"]), knobs
         assert np.array_equal(obs, ref["obs"].astype(np.float32)), knobs
+        _reach(env, _knobs(knobs))
         env.close()
 
 

@@ -94,3 +94,30 @@ def test_two_sender_token_pass_model(model2, lanes, per_lane):
     assert bad == 0
     passes, committed, plain = int(stats[0]), int(stats[1]), int(stats[2])
     assert passes > 1000 and committed > 5 * plain // 10      # the pass carried a good part of the packets
+
+
+@pytest.mark.parametrize("use_token", [1, 0])
+def test_two_sender_sweep_passes_model(model2, use_token):
+    """The two sweep formulations of heavy_mi2 -- the 256-position sweep pass (four positions per lane) and the 64-lane
+    pass settled side by side (one position per lane), without tu >= maxq and tu + tu >= tend_max -- lane by lane and
+    sweep by sweep as the kernel computes them, inside heavy_mi2's own choice of passes, against the plain merged
+    recurrence: the token pass's generators, links that keep running empty (what stops a token pass) and busy periods
+    over a whole pass with no early fixed point.  With the token pass first (the kernel's order; the sweeps get what
+    it leaves) and without it (the sweeps get everything).  A lane is final one sweep after the lane below it, so a
+    256-position pass never takes more than lanes + 1 = 65 sweeps (sweep 0 starts every lane, lane 0 too, from a drained
+    queue) and a 64-lane pass never more than 64 (its first sweep already hands lane 0 the pass's start state); the
+    worst-case generator makes both take exactly that many, and one sweep fewer in either leaves mismatches."""
+    model2.pcc_model2_fuzz_sweeps.restype = ctypes.c_long
+    model2.pcc_model2_fuzz_sweeps.argtypes = [ctypes.c_long, ctypes.c_uint64, ctypes.c_int, ctypes.POINTER(ctypes.c_uint64)]
+    stats = (ctypes.c_uint64 * 14)()
+    bad = model2.pcc_model2_fuzz_sweeps(6000, 991 + use_token, use_token, stats)
+    s = [int(v) for v in stats]
+    (tok_passes, tok_pk, s256_passes, s256_pk, s256_sweeps, s256_max, s64_passes, s64_pk, s64_sweeps, s64_max,
+     plain_passes, plain_pk, n_empty, n_busy) = s
+    assert bad == 0, s
+    assert n_empty > 500 and n_busy > 500, s                                # both new generators were drawn
+    assert s256_passes > 1000 and s256_pk > 100 * s256_passes, s            # both formulations ran, and carried packets
+    assert s64_passes > 1000 and s64_pk > 20 * s64_passes, s
+    assert (tok_passes > 1000) == bool(use_token), s
+    lanes = 64
+    assert s256_max == lanes + 1 and s64_max == lanes, s                    # the worst case was met, and never exceeded

@@ -151,5 +151,35 @@ def build_info(lib=None):
 
 
 def build_variants(force=False, verbose=False):
-    """The variant libraries of VARIANTS (see there); returns {name: path}."""
-    return {name: build_library(force=force, verbose=verbose, extra_flags=flags, out=variant_path(name)) for name, flags in VARIANTS.items()}
+    """The variant libraries of VARIANTS (see there) and the test harness of rtt_means; returns {name: path} of the variants."""
+    out = {name: build_library(force=force, verbose=verbose, extra_flags=flags, out=variant_path(name)) for name, flags in VARIANTS.items()}
+    build_rtt_harness(force=force, verbose=verbose)
+    return out
+
+
+# tests/kernels/rtt_means_harness.hip: rtt_means<8> and <16> of csrc/pcc_retire_env.h behind one C entry, for tests/test_rtt_means.py.
+# A library of its own next to the variants -- never a unit of libpcc_sim.so -- compiled with the product's flags as they are
+# (-ffp-contract=off is part of what the routine promises).
+RTT_HARNESS_SRC = os.path.join(ROOT, "tests", "kernels", "rtt_means_harness.hip")
+RTT_HARNESS_LIB = os.path.join(LIB_DIR, "libpcc_rtt_harness.so")
+
+
+def build_rtt_harness(force=False, verbose=False):
+    """Compile the harness if it is missing or older than its source or the headers; returns its path -- None, and nothing is
+    built, in a tree that has no tests/ (the harness is test infrastructure: the product builds without it)."""
+    lib = RTT_HARNESS_LIB
+    if not os.path.exists(RTT_HARNESS_SRC):
+        return None
+    if not force and os.path.exists(lib) and os.path.getmtime(lib) >= max(os.path.getmtime(p) for p in [RTT_HARNESS_SRC] + HEADERS):
+        return lib
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    if not os.path.exists(hipcc):
+        raise RuntimeError("hipcc not found; cannot build %s" % lib)
+    os.makedirs(LIB_DIR, exist_ok=True)
+    cmd = [hipcc] + HIPCC_FLAGS + ["-I", INCLUDE, "-I", CSRC, "-shared", RTT_HARNESS_SRC, "-o", lib]
+    if verbose:
+        print(" ".join(cmd))
+    p = subprocess.run(cmd, stderr=subprocess.PIPE, universal_newlines=True)
+    if p.returncode != 0:
+        raise RuntimeError("%s failed:\n%s" % (" ".join(cmd), p.stderr[-4000:]))
+    return lib

@@ -529,7 +529,9 @@ __device__ __noinline__ LeafPair leaf_sum2(const double2 *ring, uint32_t mask, u
 // np.add.reduce over ring[beg, beg + n) as a resumable walk: next() names the next leaf, feed()
 // takes its sum.  8192-sample chunks left to right; inside a chunk DOUBLE_pairwise_sum's
 // recursion (split n -> n/2 rounded down to a multiple of 8 | rest, until <= 128) walked left to
-// right with an explicit stack (depth <= 6).
+// right with an explicit stack (depth <= 7 = kWalkDepth: reached only by a chunk of 7689 .. 8191 samples, down its right-most
+// path -- 8191 -> 4103 -> 2055 -> 1031 -> 519 -> 263 -> 135 -> 71; a full chunk of 8192, and so every longer list, is 6 deep;
+// tests/test_rtt_means_cpu.py counts it for every n of a chunk).
 // The stack lives in LDS, a row per 8-lane subgroup (the lanes of a subgroup walk the same list: they write the same sizes;
 // the sums are lane 0's -- the leaf code returns them there -- and only that lane writes them).  In registers every access was
 // a chain of selects over the 7 levels (a dynamically indexed array goes to scratch memory): ~300 of the ~650 instructions

@@ -102,13 +102,17 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--normalize-obs", action="store_true",
                     help="train with PPO(normalize_obs=True); the held-out evaluation applies the trained, frozen normaliser")
+    ap.add_argument("--normalize-reward", action="store_true",
+                    help="train with PPO(normalize_reward=True); the curve's returns and the held-out evaluation stay raw, and every curve "
+                    "point carries the value loss")
     ap.add_argument("--episode-ledger", action="store_true",
                     help="train with PPO(track_episodes=True): true_mean_episode_return and episodes in every curve point, and the "
                     "held-out evaluation through pcc_rl_amd.evaluate (the library's episode ledger)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device=dev, seed=args.seed)
-    agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs, track_episodes=args.episode_ledger)
+    agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs, track_episodes=args.episode_ledger,
+                normalize_reward=args.normalize_reward)
     untrained = {k: v.clone() for k, v in agent.policy.state_dict().items()}
     iters = max(1, int(round(args.env_steps / (args.envs * args.horizon))))
     curve = []
@@ -117,7 +121,7 @@ def main():
         s = agent.iterate()
         curve.append({"iteration": it, "env_steps": (it + 1) * args.envs * args.horizon,
                       "mean_episode_return": s["mean_step_reward"] * env.max_steps, "mean_step_reward": s["mean_step_reward"],
-                      "entropy": s.get("entropy"), "wall_s": time.perf_counter() - t0})
+                      "entropy": s.get("entropy"), "value_loss": s.get("vf"), "wall_s": time.perf_counter() - t0})
         if args.episode_ledger:
             curve[-1].update(true_mean_episode_return=s["mean_episode_return"], episodes=s["episodes"])
     train_s = time.perf_counter() - t0
@@ -156,7 +160,7 @@ def main():
     by = {r["controller"]: r for r in results}
     out = {"what": "PPO (reference hyper-parameters, pi/vf MLP 32-16) on the MI355X simulator, then the trained controller against "
                    "baselines on held-out envs; python examples/learning_curve.py",
-           "normalize_obs": bool(args.normalize_obs), "episode_ledger": bool(args.episode_ledger),
+           "normalize_obs": bool(args.normalize_obs), "normalize_reward": bool(args.normalize_reward), "episode_ledger": bool(args.episode_ledger),
            "training": {"envs": args.envs, "horizon": args.horizon, "iterations": iters, "env_steps": iters * args.envs * args.horizon,
                         "reference_budget_env_steps": 6 * 1600 * 410, "wall_s": train_s,
                         "env_steps_per_s_incl_learning": iters * args.envs * args.horizon / train_s,

@@ -52,6 +52,10 @@ def main():
                     help="every member standardises its observations with its own running moments on the device "
                     "(PopulationPPO(normalize_obs=True)); the normalisers travel in --checkpoint / --resume, --save and --export, and "
                     "with the weights in a --pbt-every generation")
+    ap.add_argument("--normalize-reward", action="store_true",
+                    help="every member divides the rewards its advantage estimation reads by the running standard deviation of its own "
+                    "discounted return, with its own gamma (PopulationPPO(normalize_reward=True)); the statistics travel in --checkpoint / "
+                    "--resume and with the weights in a --pbt-every generation; scores and what is printed stay raw")
     ap.add_argument("--export", default="", help="write every member's policy as TorchScript into <dir>/member<m> (export.export_policy)")
     ap.add_argument("--checkpoint", default="", help="write the whole training state here every --checkpoint-every iterations and at the end")
     ap.add_argument("--checkpoint-every", type=int, default=10)
@@ -77,7 +81,7 @@ def main():
                         lr=values(args.lrs, 1e-3), ent_coef=values(args.ent_coefs, 0.01),
                         gamma=values(args.gammas, 0.99),
                         seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None, normalize_obs=args.normalize_obs,
-                        track_episodes=ledger)
+                        track_episodes=ledger, normalize_reward=args.normalize_reward)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)

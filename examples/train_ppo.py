@@ -30,6 +30,9 @@ def main():
     ap.add_argument("--normalize-obs", action="store_true",
                     help="standardise the observations with running moments on the device (PPO(normalize_obs=True)); the normaliser "
                     "travels in --checkpoint / --resume, in --save and in --export")
+    ap.add_argument("--normalize-reward", action="store_true",
+                    help="divide the rewards the advantage estimation reads by the running standard deviation of the discounted return, on the "
+                    "device (PPO(normalize_reward=True)); the statistics travel in --checkpoint / --resume; what is printed stays raw")
     ap.add_argument("--export", default="", help="write the trained policy here as TorchScript (export.export_policy)")
     ap.add_argument("--policy-in-step", action="store_true",
                     help="collect each horizon as one closed-loop call (pcc_rollout): the policy inside the env's launches")
@@ -43,7 +46,7 @@ def main():
     pools = tuple(int(x) for x in args.ring_pools.split(",")) if args.ring_pools else ((2, 8, 32) if args.checkpoint or args.resume else None)
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0, ring_pools=pools)
     agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
-                policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs)
+                policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs, normalize_reward=args.normalize_reward)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)

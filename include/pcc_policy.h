@@ -211,6 +211,52 @@ int pcc_episode_update(const float *reward, const uint8_t *done, const double *s
                        int64_t n_envs, double *carry, int32_t *carry_len, double *last, int32_t *last_len, double *totals,
                        int64_t totals_stride, double *scratch, void *stream);
 
+/*
+ * Reward normalisation: the running per-member variance of every env's discounted return, and the reward
+ * rows divided by its square root and clipped -- the norm_reward half of stable-baselines' VecNormalize, from the [T][n_envs] rows a
+ * rollout already holds.  One sender.  All buffers are caller-owned device memory; everything is enqueued on `stream`, nothing
+ * synchronizes.  Member m owns the columns [m * n_envs / n_members, (m + 1) * n_envs / n_members), as above.
+ * reward    [T][n_envs] float32; done [T][n_envs] uint8, != 0: env i's episode ended with step t
+ * hyper     the population's [n_members][8] float32 block: column 3 is the member's gamma, as pcc_gae_pop reads it
+ * ret_carry float64 [n_envs]: every env's running discounted return; all zeros is the empty state
+ * stats     float64 [n_members][stat_stride], stat_stride >= 3: row m is {count, mean, m2} of the member's samples, m2 the sum of
+ *           squared deviations; the padding is never read or written; all zeros is the empty state
+ * scale     float32 [n_members], or NULL
+ * scratch   pcc_return_scratch_doubles(T, n_envs, n_members) doubles (host only; -1 outside the domain)
+ *
+ * pcc_return_stats_update_pop, two launches.  For every env i of member m, with R = ret_carry[i], for t = 0 .. T - 1 in this order:
+ * R = R * (double)gamma_m + (double)reward[t][i], one float64 multiplication and one float64 addition, no contraction; this R is
+ * one sample of member m's batch; then, if done[t][i] != 0, R = 0 (VecNormalize's order: the sample is taken before the reset).
+ * R goes back to ret_carry[i].  So ret_carry is specified bit for bit, and a call over [0, T) and two calls over [0, T1) and
+ * [T1, T) leave the same bits in it.  The batch's moments (n_b = T * n_envs / n_members, mean_b, m2_b) are accumulated in float64 in
+ * a fixed order that is the implementation's: lane = env reduces its own T samples in step order, a workgroup of 256 lanes its
+ * lanes in a fixed tree, one workgroup per member the workgroups' partials in index order.  They are merged into row m of stats by
+ * Chan's formula as stated for the observation moments above -- a row with count == 0 becomes the batch's moments; count is exact
+ * -- and, if scale != NULL, scale[m] = (float)(1.0 / sqrt(m2 / count + eps)): IEEE float64 arithmetic, rounded to float32 once.
+ * Finite rewards are the contract: a NaN or an infinity is carried like any other value and spoils the env's running return
+ * until its next done, and the member's moments.
+ *
+ * pcc_reward_normalise_pop, one launch over the [T][n_envs] rows: out = fminf(fmaxf(r * scale[m], -clip), clip), m the member that
+ * owns the column: two float32 operations, no mean shift (as VecNormalize).  out == reward is allowed.
+ *
+ * No atomics, no hand-off between workgroups: the same inputs give the same bits, and a member's row, scale, ret_carry and out are
+ * bit-identical to the stand-alone call on a contiguous copy of its columns (a member is cut into workgroups exactly as a launch
+ * over the member alone; no divisibility is asked of the member size).  pcc_return_stats_update / pcc_reward_normalise are the
+ * stand-alone forms: the same kernels with one member, stat_stride = 3, gamma as an argument and scale[1].
+ * Returns 0; -1, with nothing written and before any device call, outside T >= 1, n_envs >= 1, 1 <= n_members <= 1024,
+ * n_envs % n_members == 0, stat_stride >= 3, eps >= 0, clip > 0, or for a NULL reward / done / hyper / ret_carry / stats / scratch /
+ * out (pcc_reward_normalise_pop: a NULL scale too); -3 launch failure.
+ */
+int pcc_return_scratch_doubles(int T, int64_t n_envs, int n_members);
+int pcc_return_stats_update_pop(const float *reward, const uint8_t *done, int T, int64_t n_envs, int n_members,
+                                const float *hyper, double *ret_carry, double *stats, int64_t stat_stride, float *scale,
+                                double eps, double *scratch, void *stream);
+int pcc_reward_normalise_pop(const float *reward, int T, int64_t n_envs, int n_members, const float *scale, float clip,
+                             float *out, void *stream);
+int pcc_return_stats_update(const float *reward, const uint8_t *done, int T, int64_t n_envs, float gamma, double *ret_carry,
+                            double *stats, float *scale, double eps, double *scratch, void *stream);
+int pcc_reward_normalise(const float *reward, int T, int64_t n_envs, const float *scale, float clip, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

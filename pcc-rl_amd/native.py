@@ -49,7 +49,9 @@ SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params",
            "pcc_policy_act", "pcc_ppo_supported", "pcc_ppo_scratch_floats", "pcc_ppo_minibatch_step", "pcc_gae",
            "pcc_policy_act_pop", "pcc_ppo_minibatch_step_pop", "pcc_gae_pop", "pcc_pbt_evolve",
            "pcc_obs_stats_scratch_doubles", "pcc_obs_stats_update_pop", "pcc_obs_normalise_pop", "pcc_obs_stats_update", "pcc_obs_normalise",
-           "pcc_episode_scratch_doubles", "pcc_episode_update_pop", "pcc_episode_update"]
+           "pcc_episode_scratch_doubles", "pcc_episode_update_pop", "pcc_episode_update",
+           "pcc_return_scratch_doubles", "pcc_return_stats_update_pop", "pcc_reward_normalise_pop", "pcc_return_stats_update",
+           "pcc_reward_normalise"]
 
 
 class PccError(RuntimeError):
@@ -160,6 +162,16 @@ def lib():
     L.pcc_episode_update_pop.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), i32, i32, i64, i32, vp, vp, vp, vp, vp, i64, vp, vp]
     L.pcc_episode_update.restype = i32
     L.pcc_episode_update.argtypes = [vp, vp, vp, ctypes.POINTER(ctypes.c_int32), i32, i32, i64, vp, vp, vp, vp, vp, i64, vp, vp]
+    L.pcc_return_scratch_doubles.restype = i32
+    L.pcc_return_scratch_doubles.argtypes = [i32, i64, i32]
+    L.pcc_return_stats_update_pop.restype = i32
+    L.pcc_return_stats_update_pop.argtypes = [vp, vp, i32, i64, i32, vp, vp, vp, i64, vp, dbl, vp, vp]
+    L.pcc_reward_normalise_pop.restype = i32
+    L.pcc_reward_normalise_pop.argtypes = [vp, i32, i64, i32, vp, f32, vp, vp]
+    L.pcc_return_stats_update.restype = i32
+    L.pcc_return_stats_update.argtypes = [vp, vp, i32, i64, f32, vp, vp, vp, dbl, vp, vp]
+    L.pcc_reward_normalise.restype = i32
+    L.pcc_reward_normalise.argtypes = [vp, i32, i64, vp, f32, vp, vp]
     L.pcc_debug_pass_stats.restype = i32
     L.pcc_debug_pass_stats.argtypes = [vp, vp, i32]
     L.pcc_debug_path_stats.restype = i32

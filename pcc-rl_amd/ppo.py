@@ -22,7 +22,8 @@ Two trainers share this module.  PPO is the single policy
 loop, the framework loop), the update the fused step or autograd.  PopulationPPO is K learners on slices of one env batch, one
 library call per stage for all of them, and evolve() between generations.  What the two have in common is written once:
 _RolloutRows (the buffers of a rollout, the observation normaliser's place in it, the fused loop, and the hand-over of the reward
-and done rows to the episode ledger of track_episodes=True: DESIGN.md section 21), _Trainer (the options, the first observation, the
+and done rows to the episode ledger of track_episodes=True: DESIGN.md section 21, and to the reward normaliser of
+normalize_reward=True: section 22), _Trainer (the options, the first observation, the
 checkpoint's common part) and native.call / native.current_stream.  They stay two classes: PPO draws its
 permutations with randperm and takes the last value from the torch module, and a merge would change its numbers.
 """
@@ -35,6 +36,7 @@ from .env import BatchedNetworkEnv, _ptr
 from .native import call, current_stream, lib
 from .episodes import EpisodeLedger
 from .obsnorm import ObsNormalizer
+from .rewnorm import RewardNormalizer
 
 
 class AlignedLinear(nn.Linear):
@@ -245,12 +247,18 @@ class _RolloutRows(object):
     def finish(self, agent):
         """The agent's observation for the next rollout, the normaliser's update from rows 0 .. T - 1 (what the policy saw) and,
         with track_episodes, the reward and done rows into the episode ledger (one library call, whichever way the rows were
-        filled); returns the last observation row."""
+        filled); returns the last observation row.  With normalize_reward the raw reward and done rows then update the reward
+        normaliser, and the same rows, scaled with the updated statistics (as VecNormalize does: the first rollout is not divided
+        by nothing), are what the advantage estimation reads: self.rew_gae, kept as agent.rew_norm_b.  self.rew stays raw."""
         T = self.T
         agent.obs = self.obs[T].clone()
         if agent.track_episodes:
             agent._episodes_before = agent.ledger.totals()[:, :3].clone()
             agent.ledger.update(self.rew, self.done)
+        self.rew_gae = self.rew
+        if agent.normalize_reward:
+            agent.rew_norm.update(self.rew, self.done, agent._reward_gamma())
+            self.rew_gae = agent.rew_norm_b = agent.rew_norm.normalise(self.rew)
         if self.norm is not None:
             agent.raw_b, agent.raw_obs = self.dst, self.dst[T].clone()
             self.norm.update(self.dst[:T])
@@ -272,6 +280,19 @@ class _Trainer(object):
         if hasattr(env, "groups"):
             raise ValueError("normalize_obs=True is not supported over a GroupedNetworkEnv: its groups are stepped on their own streams "
                              "and the policy reads the raw observation rows there")
+
+    def _set_reward_norm(self, env, normalize_reward, clip_reward, norm_eps, members=1):
+        """normalize_reward: a rewnorm.RewardNormalizer over the env batch, fed by every rollout after it ended (DESIGN.md section
+        22): it works with every rollout path."""
+        self.normalize_reward, self.rew_norm, self.rew_norm_b = bool(normalize_reward), None, None
+        if not self.normalize_reward:
+            return
+        if torch.device(env.device).type != "cuda":
+            raise ValueError("normalize_reward=True runs HIP kernels: it needs the env on the GPU (device=%r); there is no CPU path"
+                             % (env.device,))
+        if env.n_senders != 1:
+            raise ValueError("normalize_reward=True needs one sender per env (n_senders = %d): the normaliser's rows are [T][n_envs]" % env.n_senders)
+        self.rew_norm = RewardNormalizer(int(env.n_envs), members, clip_reward, norm_eps, device=env.device)
 
     def _set_episodes(self, env, track_episodes, members=1):
         """track_episodes: an episodes.EpisodeLedger over the env batch, fed by every rollout."""
@@ -311,8 +332,8 @@ class _Trainer(object):
     def _common_state(self):
         """The keys both state_dict()s end with: the observation the next rollout starts from, torch's CPU and device generator
         states (the rollout's noise and the minibatch permutations come from the device's), the env's snapshot, and with
-        normalize_obs the normaliser and the raw observation, with track_episodes the episode ledger (without an option the keys
-        are what they were before it)."""
+        normalize_obs the normaliser and the raw observation, with track_episodes the episode ledger, with normalize_reward the
+        reward normaliser (without an option the keys are what they were before it)."""
         dev = torch.device(self.env.device)
         sd = {"obs": self.obs.detach().clone(), "torch_rng": torch.get_rng_state(),
               "device_rng": torch.cuda.get_rng_state(dev) if dev.type == "cuda" else None, "env": self.env.snapshot()}
@@ -320,6 +341,8 @@ class _Trainer(object):
             sd.update(normalize_obs=True, obs_norm=self.obs_norm.state_dict(), raw_obs=self.raw_obs.detach().clone())
         if self.track_episodes:
             sd.update(track_episodes=True, episodes=self.ledger.state_dict())
+        if self.normalize_reward:
+            sd.update(normalize_reward=True, rew_norm=self.rew_norm.state_dict())
         return sd
 
     def _restore(self, sd):
@@ -334,8 +357,14 @@ class _Trainer(object):
         if theirs != self.track_episodes:
             raise ValueError("the checkpoint was written with track_episodes=%s, this object has track_episodes=%s: the running "
                              "episodes of the env's snapshot and the ledger belong together" % (theirs, self.track_episodes))
+        theirs = bool(sd.get("normalize_reward", False))
+        if theirs != self.normalize_reward:
+            raise ValueError("the checkpoint was written with normalize_reward=%s, this object has normalize_reward=%s: a value "
+                             "network without the scale of its targets is meaningless" % (theirs, self.normalize_reward))
         self.env.restore(sd["env"])
         self._load_params(sd)
+        if self.normalize_reward:
+            self.rew_norm.load_state_dict(sd["rew_norm"])
         if self.track_episodes:
             self.ledger.load_state_dict(sd["episodes"])
         self.obs = sd["obs"].to(dev).clone()
@@ -350,7 +379,7 @@ class _Trainer(object):
 class PPO(_Trainer):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
                  epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
-                 normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False):
+                 normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False, normalize_reward=False, clip_reward=10.0):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
         optimiser steps per epoch, thousands of launches of a few microseconds of work each.
@@ -359,13 +388,18 @@ class PPO(_Trainer):
         normalize_obs: the policy sees clamp((obs - mean) / sqrt(var + norm_eps), -clip_obs, clip_obs) with the running moments of
         the raw rows (obsnorm.ObsNormalizer): frozen during a rollout, updated once at its end.
         track_episodes: every rollout's reward and done rows go into an episode ledger (episodes.EpisodeLedger, self.ledger) and
-        iterate() adds episodes, mean_episode_return and mean_episode_length of the episodes that rollout finished."""
+        iterate() adds episodes, mean_episode_return and mean_episode_length of the episodes that rollout finished.
+        normalize_reward: the advantage estimation reads clamp(reward / sqrt(var + norm_eps), -clip_reward, clip_reward), var the
+        running variance of every env's discounted return (rewnorm.RewardNormalizer, self.rew_norm), updated
+        at the end of a rollout and applied to that rollout's rows (self.rew_norm_b).  What collect() returns and iterate() reports
+        stays raw."""
         if policy_in_step and torch.device(env.device).type != "cuda":
             raise ValueError("PPO(policy_in_step=True) runs the policy inside the env's HIP launches: it needs the env on the GPU "
                              "(device=%r)" % (env.device,))
         self.policy_in_step = bool(policy_in_step)
         self._set_normalize(env, normalize_obs, policy_in_step)
         self._set_episodes(env, track_episodes)
+        self._set_reward_norm(env, normalize_reward, clip_reward, norm_eps)
         self.env, self.gamma, self.lam, self.clip, self.ent_coef = env, gamma, lam, clip, ent_coef
         self.epochs, self.minibatch, self.horizon = epochs, minibatch, horizon
         torch.manual_seed(seed)
@@ -423,8 +457,12 @@ class PPO(_Trainer):
         # never train on corrupted rollouts: an overflowed in-flight ring / an empty ring pool (a trained
         # policy can push many deep-queue envs to MAX_RATE: BatchedNetworkEnv(ring_pools=...)) is flagged, not silent
         env.check_flags()
-        adv, ret = (gae_fused if fused else gae)(rows.rew, rows.val, rows.done, last_v, self.gamma, self.lam)
+        adv, ret = (gae_fused if fused else gae)(rows.rew_gae, rows.val, rows.done, last_v, self.gamma, self.lam)
+        self.val_b, self.done_b = rows.val, rows.done
         return rows.obs[:T], rows.act, rows.logp, adv, ret, rows.rew
+
+    def _reward_gamma(self):
+        return self.gamma
 
     def _rollout_in_step(self, rows, params, noise):
         """The whole horizon as one pcc_rollout per env (group): the same noise, parameters and rows as the fused loop."""
@@ -652,7 +690,8 @@ class PopulationPPO(_Trainer):
     for raises ValueError."""
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
-                 epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False):
+                 epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False,
+                 normalize_reward=False, clip_reward=10.0):
         members = int(members)
         self._set_normalize(env, normalize_obs)
         if members < 1 or members > 1024:
@@ -671,6 +710,7 @@ class PopulationPPO(_Trainer):
             raise ValueError("PopulationPPO: the library has no kernels for %d observations x hidden %s (pcc_ppo_supported)"
                              % (env.obs_dim, list(arch)))
         self._set_episodes(env, track_episodes, members)
+        self._set_reward_norm(env, normalize_reward, clip_reward, norm_eps, members)
         self.env, self.members, self.arch = env, members, (int(arch[0]), int(arch[1]))
         self.epochs, self.horizon, self.adam_eps = epochs, horizon, 1e-5
         self.n_member = int(env.n_envs) // members
@@ -725,9 +765,12 @@ class PopulationPPO(_Trainer):
         last_v = torch.empty(N, device=env.device)
         self._act(rows.finish(self), None, None, None, last_v)
         env.check_flags()
-        adv, ret = self._gae(rows.rew, rows.val, rows.done, last_v)
+        adv, ret = self._gae(rows.rew_gae, rows.val, rows.done, last_v)
         self.val_b, self.done_b = rows.val, rows.done
         return rows.obs[:T], rows.act, rows.logp, adv, ret, rows.rew
+
+    def _reward_gamma(self):
+        return self.hyper   # (every member's own gamma, as the device holds it now: column 3)
 
     def normalise(self, adv):
         return normalise_per_member(adv, self.members)
@@ -805,6 +848,8 @@ class PopulationPPO(_Trainer):
             self.ledger.inherit(parent)
             if own:
                 self.ledger.clear()
+        if self.normalize_reward:   # the value network's targets are in its parent's scale
+            self.rew_norm.inherit(parent)
         self.generation += 1
         self.hyper_rows = None
         return parent, rank

@@ -56,6 +56,13 @@ def main():
                     help="every member divides the rewards its advantage estimation reads by the running standard deviation of its own "
                     "discounted return, with its own gamma (PopulationPPO(normalize_reward=True)); the statistics travel in --checkpoint / "
                     "--resume and with the weights in a --pbt-every generation; scores and what is printed stay raw")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="after every epoch of an update compute the approximate KL divergence from the rollout's policy, the clip fraction over "
+                    "the whole rollout and the explained variance of the value function on the device (PopulationPPO(diagnostics=True))")
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="stop updating a member for the rest of an update once its approximate KL exceeds 1.5 x this after an epoch, decided on "
+                    "the device (implies --diagnostics)")
+    ap.add_argument("--diag-rows", type=int, default=None, help="the checks read about this many of the horizon's rows (default: all)")
     ap.add_argument("--export", default="", help="write every member's policy as TorchScript into <dir>/member<m> (export.export_policy)")
     ap.add_argument("--checkpoint", default="", help="write the whole training state here every --checkpoint-every iterations and at the end")
     ap.add_argument("--checkpoint-every", type=int, default=10)
@@ -81,7 +88,8 @@ def main():
                         lr=values(args.lrs, 1e-3), ent_coef=values(args.ent_coefs, 0.01),
                         gamma=values(args.gammas, 0.99),
                         seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None, normalize_obs=args.normalize_obs,
-                        track_episodes=ledger, normalize_reward=args.normalize_reward)
+                        track_episodes=ledger, normalize_reward=args.normalize_reward,
+                        diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)
@@ -119,6 +127,10 @@ def main():
             curve.setdefault("true_mean_episode_return", []).append(s["mean_episode_return"])
             pbt = "  episodes: %s  true return: %s%s" % (" ".join("%d" % e for e in s["episodes"]),
                                                           " ".join("%7.1f" % r for r in s["mean_episode_return"]), pbt)
+        if pop.diagnostics:
+            for key in ("approx_kl", "clip_fraction", "explained_variance", "epochs_run"):
+                curve.setdefault(key, []).append(s[key])
+            pbt = "  kl: %s  epochs: %s%s" % (" ".join("%.4f" % k for k in s["approx_kl"]), " ".join("%d" % e for e in s["epochs_run"]), pbt)
         steps = (it + 1 - first) * args.envs * args.horizon
         print("iter %3d  env-steps %11d  %.0f env-steps/s incl. learning  return per member: %s%s"
               % (it, steps, steps / (time.perf_counter() - t0), " ".join("%7.1f" % (r * env.max_steps) for r in s["mean_step_reward"]), pbt))

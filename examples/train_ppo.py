@@ -33,6 +33,13 @@ def main():
     ap.add_argument("--normalize-reward", action="store_true",
                     help="divide the rewards the advantage estimation reads by the running standard deviation of the discounted return, on the "
                     "device (PPO(normalize_reward=True)); the statistics travel in --checkpoint / --resume; what is printed stays raw")
+    ap.add_argument("--diagnostics", action="store_true",
+                    help="after every epoch of an update compute the approximate KL divergence from the rollout's policy, the clip fraction over "
+                    "the whole rollout and the explained variance of the value function on the device (PPO(diagnostics=True))")
+    ap.add_argument("--target-kl", type=float, default=None,
+                    help="stop updating the policy for the rest of an update once its approximate KL exceeds 1.5 x this after an epoch, decided on "
+                    "the device (implies --diagnostics)")
+    ap.add_argument("--diag-rows", type=int, default=None, help="the checks read about this many of the horizon's rows (default: all)")
     ap.add_argument("--export", default="", help="write the trained policy here as TorchScript (export.export_policy)")
     ap.add_argument("--policy-in-step", action="store_true",
                     help="collect each horizon as one closed-loop call (pcc_rollout): the policy inside the env's launches")
@@ -46,7 +53,8 @@ def main():
     pools = tuple(int(x) for x in args.ring_pools.split(",")) if args.ring_pools else ((2, 8, 32) if args.checkpoint or args.resume else None)
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0, ring_pools=pools)
     agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
-                policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs, normalize_reward=args.normalize_reward)
+                policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs, normalize_reward=args.normalize_reward,
+                diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)
@@ -64,8 +72,10 @@ def main():
         if args.checkpoint and ((it + 1) % max(args.checkpoint_every, 1) == 0 or it + 1 == args.iters):
             checkpoint(it + 1)
         steps = (it + 1 - first) * args.envs * args.horizon
-        print("iter %3d  env-steps %10d  reward/step %8.4f  entropy %6.3f  %.0f env-steps/s incl. learning"
-              % (it, steps, s["mean_step_reward"], s["entropy"], steps / (time.perf_counter() - t0)))
+        diag = ("  kl %.4f  clipped %.3f  explained variance %6.3f  epochs %d"
+                % (s["approx_kl"], s["clip_fraction"], s["explained_variance"], s["epochs_run"])) if agent.diagnostics else ""
+        print("iter %3d  env-steps %10d  reward/step %8.4f  entropy %6.3f  %.0f env-steps/s incl. learning%s"
+              % (it, steps, s["mean_step_reward"], s["entropy"], steps / (time.perf_counter() - t0), diag))
     obs_norm = agent.obs_norm.member(0) if args.normalize_obs else None   # (shift, scale, clip): the policy is meaningless without it
     if args.save:
         torch.save({"policy": agent.policy.state_dict(), "obs_norm": obs_norm} if args.normalize_obs else agent.policy.state_dict(), args.save)

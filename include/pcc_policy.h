@@ -257,6 +257,65 @@ int pcc_return_stats_update(const float *reward, const uint8_t *done, int T, int
                             double *stats, float *scale, double eps, double *scratch, void *stream);
 int pcc_reward_normalise(const float *reward, int T, int64_t n_envs, const float *scale, float clip, float *out, void *stream);
 
+/*
+ * Update diagnostics and the KL guard: what an update did to the policy -- per member the approximate KL
+ * divergence between the rollout's policy and the updated one, the clip fraction over the whole rollout, the explained variance of
+ * the value function -- from the [T][n_envs] rows a rollout already holds, and the per-member decision to stop updating, taken on the
+ * device.  One sender.  All buffers are caller-owned device memory; everything is enqueued on `stream`, nothing synchronizes.
+ * Member m owns the columns [m * n_envs / n_members, (m + 1) * n_envs / n_members), as above.
+ *
+ * pcc_policy_act_rows_pop: the deterministic forward (noise == NULL) of pcc_policy_act_pop on the rows t = 0, row_step, 2 row_step,
+ * ... < T of obs[T][n_envs][obs_dim], into the same rows of mean_out / value_out [T][n_envs]; either may be NULL; no other row is
+ * written.  One library call; inside it the launches are pcc_policy_act_pop's -- one per row, or, with one member and row_step == 1,
+ * one over the T * n_envs rows as a single batch -- and every output is bit-identical to calling pcc_policy_act_pop row by row.
+ * The domain and the return codes of pcc_policy_act_pop, plus -1 for T < 1 or row_step < 1;
+ * every -1 comes before any device call.
+ *
+ * pcc_update_diag_pop, two launches, over the rows t = 0, row_step, ... < T (the selected rows):
+ * act, logp_old, mean_new, ret, val   [T][n_envs] float32: the rollout's actions and log-probabilities, the UPDATED policy's means
+ *           (pcc_policy_act_rows_pop), the returns the value function was fitted to and the rollout's values
+ * params, param_stride   the population's parameter blocks; log_std = params[m * param_stride + log_std_index]
+ * hyper     the population's [n_members][8] float32 block: column 1 is the member's clip range
+ * diag      float64 [n_members][diag_stride], diag_stride >= 8: row m is {count, approx_kl, clip_fraction, explained_variance,
+ *           max_abs_log_ratio, var_ret, var_resid, nonfinite}; the padding is never read or written
+ * stop      int32 [n_members], sticky: 0, or the epoch at which the member was stopped; the caller zeroes it at the start of an
+ *           update.  hyper_live: float32 [n_members][8].  The two may be NULL only together: diagnostics alone
+ * scratch   pcc_update_diag_scratch_doubles(T, row_step, n_envs, n_members) doubles (host only; -1 outside the domain)
+ * Per sample of a selected row, in float32 without contraction: inv = expf(-log_std) (libm's), z = (act - mean_new) * inv,
+ * lp = -0.5f * z * z - log_std - log(2 pi) / 2 (the Gaussian head's log-probability), d32 = lp - logp_old.  Then in float64:
+ * d = (double)d32, k = expm1(d) - d; the sample counts as clipped iff fabs(expm1(d)) > (double)hyper[m][1]; e = (double)ret -
+ * (double)val.  approx_kl = the mean of k; clip_fraction = clipped / count; var_ret and var_resid the population variances (m2 /
+ * count) of ret and of e, accumulated as {n, mean, m2} with Chan's merge as stated for the observation moments above;
+ * explained_variance = 1 - var_resid / var_ret, NaN when var_ret == 0; max_abs_log_ratio = the maximum of fabs(d) by fmax from 0 (a
+ * NaN sample does not enter it); nonfinite = the number of samples whose d is not finite.  count, the clipped count and nonfinite
+ * are exact.  The float64 sums are added in a fixed order that is the implementation's: lane = env adds its own rows in step order,
+ * a wavefront its lanes in a fixed tree, a workgroup of 256 lanes its four wavefronts in index order, one workgroup per member the
+ * workgroups' partials in index order.
+ * The decision, per member, after its row is written, if stop != NULL: if stop[m] == 0 && kl_limit > 0 && !(approx_kl <= kl_limit)
+ * then stop[m] = epoch -- a NaN approx_kl stops the member; kl_limit <= 0 never stops.  Then hyper_live[m][0 .. 8) = hyper[m][0 .. 8)
+ * and hyper_live[m][0] = 0.0f iff stop[m] != 0: pcc_ppo_minibatch_step_pop with hyper_live in place of hyper treats a stopped member
+ * as gradient-only and leaves its parameters and moments alone.
+ *
+ * No atomics, no hand-off between workgroups: the same inputs give the same bits, and a member's row is bit-identical to the
+ * stand-alone call on a contiguous copy of its columns (a member is cut into workgroups exactly as a launch over the member alone; no
+ * divisibility is asked of the member size).  pcc_update_diag is the stand-alone form: the same kernels with one member, diag [8],
+ * the clip range as an argument, log_std = params[log_std_index], no decision.
+ * Returns 0; -1, with nothing written and before any device call, for T < 1, row_step < 1, n_envs < 1, n_members outside 1 .. 1024,
+ * n_envs % n_members != 0, diag_stride < 8, epoch < 1, log_std_index outside [0, param_stride), param_stride not a multiple of 64,
+ * a NULL act / logp_old / mean_new / ret / val / params / hyper / diag / scratch, or exactly one of stop and hyper_live NULL; -3
+ * launch failure.
+ */
+int pcc_policy_act_rows_pop(const float *obs, int T, int row_step, int64_t n_envs, int obs_dim, const float *params,
+                            int64_t param_stride, int n_members, int h1, int h2, float *mean_out, float *value_out, void *stream);
+int pcc_update_diag_scratch_doubles(int T, int row_step, int64_t n_envs, int n_members);
+int pcc_update_diag_pop(const float *act, const float *logp_old, const float *mean_new, const float *ret, const float *val, int T,
+                        int row_step, int64_t n_envs, int n_members, const float *params, int64_t param_stride, int64_t log_std_index,
+                        const float *hyper, double kl_limit, int epoch, double *diag, int64_t diag_stride, int32_t *stop,
+                        float *hyper_live, double *scratch, void *stream);
+int pcc_update_diag(const float *act, const float *logp_old, const float *mean_new, const float *ret, const float *val, int T,
+                    int row_step, int64_t n_envs, const float *params, int64_t log_std_index, float clip, double *diag,
+                    double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

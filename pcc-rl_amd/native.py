@@ -51,7 +51,8 @@ SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params",
            "pcc_obs_stats_scratch_doubles", "pcc_obs_stats_update_pop", "pcc_obs_normalise_pop", "pcc_obs_stats_update", "pcc_obs_normalise",
            "pcc_episode_scratch_doubles", "pcc_episode_update_pop", "pcc_episode_update",
            "pcc_return_scratch_doubles", "pcc_return_stats_update_pop", "pcc_reward_normalise_pop", "pcc_return_stats_update",
-           "pcc_reward_normalise"]
+           "pcc_reward_normalise",
+           "pcc_policy_act_rows_pop", "pcc_update_diag_scratch_doubles", "pcc_update_diag_pop", "pcc_update_diag"]
 
 
 class PccError(RuntimeError):
@@ -172,6 +173,14 @@ def lib():
     L.pcc_return_stats_update.argtypes = [vp, vp, i32, i64, f32, vp, vp, vp, dbl, vp, vp]
     L.pcc_reward_normalise.restype = i32
     L.pcc_reward_normalise.argtypes = [vp, i32, i64, vp, f32, vp, vp]
+    L.pcc_policy_act_rows_pop.restype = i32
+    L.pcc_policy_act_rows_pop.argtypes = [vp, i32, i32, i64, i32, vp, i64, i32, i32, i32, vp, vp, vp]
+    L.pcc_update_diag_scratch_doubles.restype = i32
+    L.pcc_update_diag_scratch_doubles.argtypes = [i32, i32, i64, i32]
+    L.pcc_update_diag_pop.restype = i32
+    L.pcc_update_diag_pop.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, vp, i64, i64, vp, dbl, i32, vp, i64, vp, vp, vp, vp]
+    L.pcc_update_diag.restype = i32
+    L.pcc_update_diag.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, vp, i64, f32, vp, vp, vp]
     L.pcc_debug_pass_stats.restype = i32
     L.pcc_debug_pass_stats.argtypes = [vp, vp, i32]
     L.pcc_debug_path_stats.restype = i32

@@ -23,7 +23,8 @@ loop, the framework loop), the update the fused step or autograd.  PopulationPPO
 library call per stage for all of them, and evolve() between generations.  What the two have in common is written once:
 _RolloutRows (the buffers of a rollout, the observation normaliser's place in it, the fused loop, and the hand-over of the reward
 and done rows to the episode ledger of track_episodes=True: DESIGN.md section 21, and to the reward normaliser of
-normalize_reward=True: section 22), _Trainer (the options, the first observation, the
+normalize_reward=True: section 22), _Trainer (the options -- among them the update diagnostics and the KL guard of
+diagnostics=True / target_kl: updiag.UpdateDiagnostics, section 23 --, the first observation, the
 checkpoint's common part) and native.call / native.current_stream.  They stay two classes: PPO draws its
 permutations with randperm and takes the last value from the torch module, and a merge would change its numbers.
 """
@@ -37,6 +38,7 @@ from .native import call, current_stream, lib
 from .episodes import EpisodeLedger
 from .obsnorm import ObsNormalizer
 from .rewnorm import RewardNormalizer
+from .updiag import UpdateDiagnostics
 
 
 class AlignedLinear(nn.Linear):
@@ -294,6 +296,29 @@ class _Trainer(object):
             raise ValueError("normalize_reward=True needs one sender per env (n_senders = %d): the normaliser's rows are [T][n_envs]" % env.n_senders)
         self.rew_norm = RewardNormalizer(int(env.n_envs), members, clip_reward, norm_eps, device=env.device)
 
+    def _set_diagnostics(self, env, diagnostics, target_kl, diag_rows, horizon, members=1):
+        """diagnostics / target_kl: an updiag.UpdateDiagnostics over the env batch, run after every epoch of update() (DESIGN.md
+        section 23).  target_kl implies diagnostics; diag_rows=R reads about R of the horizon's rows (every max(1, T // R)-th)."""
+        self.target_kl = None if target_kl is None else float(target_kl)
+        self.diagnostics, self.diag = bool(diagnostics) or target_kl is not None, None
+        if not self.diagnostics:
+            return
+        if self.target_kl is not None and not self.target_kl > 0.0:
+            raise ValueError("target_kl = %r (> 0, or None for no guard)" % (target_kl,))
+        if diag_rows is not None and int(diag_rows) < 1:
+            raise ValueError("diag_rows = %r (>= 1, or None for every row)" % (diag_rows,))
+        if torch.device(env.device).type != "cuda":
+            raise ValueError("diagnostics=True / target_kl run HIP kernels: they need the env on the GPU (device=%r); there is no CPU path"
+                             % (env.device,))
+        if env.n_senders != 1:
+            raise ValueError("diagnostics=True / target_kl need one sender per env (n_senders = %d): the rows are [T][n_envs]" % env.n_senders)
+        row_step = 1 if diag_rows is None else max(1, int(horizon) // int(diag_rows))
+        self.diag = UpdateDiagnostics(int(env.n_envs), members, env.device, row_step)
+
+    def _kl_limit(self):
+        """What pcc_update_diag_pop stops a member at: 1.5 x the target, as stable-baselines3 and Spinning Up do; 0: no guard."""
+        return 0.0 if self.target_kl is None else 1.5 * self.target_kl
+
     def _set_episodes(self, env, track_episodes, members=1):
         """track_episodes: an episodes.EpisodeLedger over the env batch, fed by every rollout."""
         self.track_episodes, self.ledger = bool(track_episodes), None
@@ -343,6 +368,8 @@ class _Trainer(object):
             sd.update(track_episodes=True, episodes=self.ledger.state_dict())
         if self.normalize_reward:
             sd.update(normalize_reward=True, rew_norm=self.rew_norm.state_dict())
+        if self.diagnostics:   # (the options only: the buffers live for one update)
+            sd.update(diagnostics=True, target_kl=self.target_kl, diag_row_step=self.diag.row_step)
         return sd
 
     def _restore(self, sd):
@@ -361,6 +388,11 @@ class _Trainer(object):
         if theirs != self.normalize_reward:
             raise ValueError("the checkpoint was written with normalize_reward=%s, this object has normalize_reward=%s: a value "
                              "network without the scale of its targets is meaningless" % (theirs, self.normalize_reward))
+        theirs = (bool(sd.get("diagnostics", False)), sd.get("target_kl"), sd.get("diag_row_step"))
+        mine = (self.diagnostics, self.target_kl, self.diag.row_step if self.diagnostics else None)
+        if theirs != mine:
+            raise ValueError("the checkpoint was written with (diagnostics, target_kl, row step) = %s, this object has %s: the KL guard "
+                             "decides which updates are applied" % (theirs, mine))
         self.env.restore(sd["env"])
         self._load_params(sd)
         if self.normalize_reward:
@@ -379,7 +411,8 @@ class _Trainer(object):
 class PPO(_Trainer):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
                  epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
-                 normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False, normalize_reward=False, clip_reward=10.0):
+                 normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False, normalize_reward=False, clip_reward=10.0,
+                 diagnostics=False, target_kl=None, diag_rows=None):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
         optimiser steps per epoch, thousands of launches of a few microseconds of work each.
@@ -392,7 +425,19 @@ class PPO(_Trainer):
         normalize_reward: the advantage estimation reads clamp(reward / sqrt(var + norm_eps), -clip_reward, clip_reward), var the
         running variance of every env's discounted return (rewnorm.RewardNormalizer, self.rew_norm), updated
         at the end of a rollout and applied to that rollout's rows (self.rew_norm_b).  What collect() returns and iterate() reports
-        stays raw."""
+        stays raw.
+        diagnostics: after every epoch of update() the approximate KL divergence between the rollout's policy and the updated one, the
+        clip fraction over the whole rollout and the explained variance of the value function are computed on the device
+        (updiag.UpdateDiagnostics, self.diag), and update() adds approx_kl, clip_fraction, explained_variance,
+        max_log_ratio, nonfinite and epochs_run from the check after the last epoch.  The parameters are what they are without it.
+        target_kl (implies diagnostics): once the approximate KL exceeds 1.5 x target_kl after an epoch -- or is NaN -- the later
+        minibatches of this update are gradient-only (the parameters and Adam's moments stay; Adam's step count goes on), decided on
+        the device without a synchronise.  diag_rows=R: the checks read every max(1, horizon // R)-th row.  Both need the fused
+        update."""
+        if (diagnostics or target_kl is not None) and not fused_update:
+            raise ValueError("PPO(diagnostics=True / target_kl) needs the fused update (fused_update=True): the framework path has no "
+                             "diagnostics")
+        self._set_diagnostics(env, diagnostics, target_kl, diag_rows, horizon)
         if policy_in_step and torch.device(env.device).type != "cuda":
             raise ValueError("PPO(policy_in_step=True) runs the policy inside the env's HIP launches: it needs the env on the GPU "
                              "(device=%r)" % (env.device,))
@@ -419,6 +464,12 @@ class PPO(_Trainer):
             self.adam_m, self.adam_v, self.adam_t = torch.zeros_like(self.flat), torch.zeros_like(self.flat), 0
             self.scratch = torch.empty(lib().pcc_ppo_scratch_floats(env.obs_dim, arch[0], arch[1]), device=env.device)
             self.stats_buf = torch.zeros(4, device=env.device)
+        elif self.diagnostics:
+            raise ValueError("PPO(diagnostics=True / target_kl) needs the fused update: the library has no pcc_ppo_minibatch_step for "
+                             "observation length %d, hidden %s" % (env.obs_dim, list(arch)))
+        if self.diagnostics:   # the [1][8] hyper block the checks read the clip range from, and the step of target_kl its lr
+            self.hyper = torch.zeros((1, HYPER_COLS), dtype=torch.float32, device=env.device)   # (filled at every update: _hyper_now)
+            self.param_stride = (self.flat.numel() + 63) // 64 * 64   # (one member: the padding is never read or written)
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=lr, eps=self.adam_eps)
         self._first_obs(1, clip_obs, norm_eps)
         if self.minibatch is None:
@@ -529,7 +580,9 @@ class PPO(_Trainer):
         logp_f, adv_f, ret_f = logp_b.reshape(n), adv.reshape(n), ret.reshape(n)
         adv_f = (adv_f - adv_f.mean()) / (adv_f.std() + 1e-8)
         if self.fused_update:
-            return self._update_fused(obs_f, act_f, logp_f, adv_f, ret_f)
+            if self.diagnostics and obs_b.dim() != 3:
+                raise ValueError("PPO(diagnostics=True).update needs the rollout's [T][N][D] observation rows, as collect() returns them")
+            return self._update_fused(obs_f, act_f, logp_f, adv_f, ret_f, obs_b.shape[0])
         stats = {}
         for _ in range(self.epochs):
             perm = torch.randperm(n, device=obs_f.device)
@@ -558,17 +611,45 @@ class PPO(_Trainer):
              lr, 0.9, 0.999, self.adam_eps, self.clip, self.ent_coef, _ptr(self.scratch),
              _ptr(grad_out), _ptr(self.stats_buf), current_stream(obs_f.device))
 
-    def _update_fused(self, obs_f, act_f, logp_f, adv_f, ret_f):
+    def _hyper_now(self):
+        """self.hyper from lr, clip, ent_coef, gamma and lam as they are NOW: a caller may change them between updates (a schedule),
+        and the guarded step and the checks must see what minibatch_step_fused would pass."""
+        row = [[self.lr, self.clip, self.ent_coef, self.gamma, self.lam] + [0.0] * (HYPER_COLS - len(HYPER_NAMES))]
+        self.hyper.copy_(torch.tensor(row, dtype=torch.float32))
+        return self.hyper
+
+    def _minibatch_step_guarded(self, obs_f, act_f, logp_f, adv_f, ret_f, perm, start, count):
+        """minibatch_step_fused under target_kl: pcc_ppo_minibatch_step_pop with ONE member and the checks' hyper_live as its hyper
+        block -- bit-identical to pcc_ppo_minibatch_step while the member is live, gradient-only once the
+        kernel has stopped it."""
+        if self.lr != 0.0:   # (as minibatch_step_fused: a gradient-only step is no step of Adam's)
+            self.adam_t += 1
+        h1, h2 = self.policy.hidden
+        call("pcc_ppo_minibatch_step_pop", _ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), perm.numel(),
+             start, count, obs_f.shape[1], h1, h2, _ptr(self.flat), _ptr(self.adam_m), _ptr(self.adam_v), self.param_stride, 1,
+             _ptr(self.diag.hyper_live), max(self.adam_t, 1), 0.9, 0.999, self.adam_eps, _ptr(self.scratch), None, _ptr(self.stats_buf),
+             current_stream(obs_f.device))
+
+    def _update_fused(self, obs_f, act_f, logp_f, adv_f, ret_f, T=None):
         n = obs_f.shape[0]
         obs_f, act_f = obs_f.contiguous(), act_f.reshape(n).contiguous()
         logp_f, adv_f, ret_f = logp_f.contiguous(), adv_f.contiguous(), ret_f.contiguous()
-        for _ in range(self.epochs):
+        step = self.minibatch_step_fused if self.target_kl is None else self._minibatch_step_guarded
+        if self.diagnostics:
+            self.diag.begin(self._hyper_now())
+        for e in range(self.epochs):
             perm = torch.randperm(n, device=obs_f.device)
             for i in range(0, n, self.minibatch):
-                self.minibatch_step_fused(obs_f, act_f, logp_f, adv_f, ret_f, perm, i, min(self.minibatch, n - i))
+                step(obs_f, act_f, logp_f, adv_f, ret_f, perm, i, min(self.minibatch, n - i))
+            if self.diagnostics:   # what this epoch did, and whether the next one still updates
+                self.diag.check(e + 1, obs_f.view(T, n // T, -1), act_f, logp_f, ret_f, self.val_b.contiguous(), self.flat,
+                                self.param_stride, self.flat.numel(), self.policy.hidden, self.hyper, self._kl_limit())
         st = self.stats_buf.tolist()   # of the last minibatch, like the framework path
         ent = float(self.policy.log_std.detach().sum()) + 0.5 * (1.0 + math.log(2.0 * math.pi)) * self.policy.log_std.numel()
-        return {"pg": -st[0], "vf": 0.5 * st[1], "entropy": ent, "clip_frac": st[2]}
+        out = {"pg": -st[0], "vf": 0.5 * st[1], "entropy": ent, "clip_frac": st[2]}
+        if self.diagnostics:
+            out.update({k: v[0] for k, v in self.diag.report(self.epochs).items()})
+        return out
 
     def state_dict(self):
         """Everything the next iterate() depends on, for a checkpoint that resumes bit for bit: the parameters and Adam's state (the
@@ -687,11 +768,17 @@ class PopulationPPO(_Trainer):
     member.  Member m's policy starts as PPO(seed=seeds[m])'s: like PPO, construction reseeds torch's global generators
     (torch.manual_seed, member by member), so they are left seeded by seeds[-1], and the rollout's noise and the minibatch
     permutations are drawn from the device's from there.  There is no framework path: anything the library has no kernel
-    for raises ValueError."""
+    for raises ValueError.
+    diagnostics / target_kl / diag_rows: PPO's options, per member: update() adds per-member lists of
+    approx_kl, clip_fraction, explained_variance, max_log_ratio, nonfinite and epochs_run.  With target_kl a member whose approximate
+    KL after an epoch exceeds 1.5 x target_kl, or is NaN (its parameters have gone non-finite), is stopped for the rest of that
+    update: its later minibatches are gradient-only, exactly as an lr == 0 member's are -- its parameters and Adam's moments stay as
+    they are -- while the other members go on; Adam's step count stays the population's (it goes on for the stopped member too).  The
+    decision is the kernel's: no copy to the host, no synchronise."""
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
                  epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False,
-                 normalize_reward=False, clip_reward=10.0):
+                 normalize_reward=False, clip_reward=10.0, diagnostics=False, target_kl=None, diag_rows=None):
         members = int(members)
         self._set_normalize(env, normalize_obs)
         if members < 1 or members > 1024:
@@ -711,6 +798,7 @@ class PopulationPPO(_Trainer):
                              % (env.obs_dim, list(arch)))
         self._set_episodes(env, track_episodes, members)
         self._set_reward_norm(env, normalize_reward, clip_reward, norm_eps, members)
+        self._set_diagnostics(env, diagnostics, target_kl, diag_rows, horizon, members)
         self.env, self.members, self.arch = env, members, (int(arch[0]), int(arch[1]))
         self.epochs, self.horizon, self.adam_eps = epochs, horizon, 1e-5
         self.n_member = int(env.n_envs) // members
@@ -777,33 +865,44 @@ class PopulationPPO(_Trainer):
 
     def minibatch_step(self, obs_f, act_f, logp_f, adv_f, ret_f, perm, start, count, grad_out=None):
         """One optimiser step of every member on its samples perm[m][start : start + count] (global indices into the flattened
-        rollout): two launches (pcc_ppo_minibatch_step_pop)."""
+        rollout): two launches (pcc_ppo_minibatch_step_pop).  With target_kl the hyper block it passes is self.diag.hyper_live, which
+        update() sets up (begin) and the checks keep: a stopped member's step is gradient-only."""
         if start < 0 or count < 1 or start + count > perm.shape[1]:
             raise ValueError("minibatch [%d, %d) outside a member's rollout" % (start, start + count))
         self.adam_t += 1
         D = obs_f.shape[1]
         call("pcc_ppo_minibatch_step_pop", _ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), perm.stride(0),
              start, count, D, self.arch[0], self.arch[1], _ptr(self.flat), _ptr(self.adam_m),
-             _ptr(self.adam_v), self.param_stride, self.members, _ptr(self.hyper), self.adam_t, 0.9, 0.999,
+             _ptr(self.adam_v), self.param_stride, self.members,
+             _ptr(self.hyper if self.target_kl is None else self.diag.hyper_live), self.adam_t, 0.9, 0.999,
              self.adam_eps, _ptr(self.scratch), _ptr(grad_out), _ptr(self.stats_buf), self._stream())
 
     def update(self, obs_b, act_b, logp_b, adv, ret, perms=None):
         """`epochs` passes over every member's own samples in minibatches of self.minibatch samples per member.  perms: one
-        [members][T * n_m] tensor per epoch (population_permutations; default: drawn here, one draw per epoch)."""
+        [members][T * n_m] tensor per epoch (population_permutations; default: drawn here, one draw per epoch).  With diagnostics
+        every epoch ends with the checks of updiag.UpdateDiagnostics on the rollout's rows (the values are self.val_b, collect()'s)."""
         T, N = adv.shape
         n = T * N
         adv_f = self.normalise(adv).reshape(n)
         obs_f, act_f = obs_b.reshape(n, -1).contiguous(), act_b.reshape(n).contiguous()
         logp_f, ret_f = logp_b.reshape(n).contiguous(), ret.reshape(n).contiguous()
         per_member = T * self.n_member
+        if self.diagnostics:
+            self.diag.begin(self.hyper)
         for e in range(self.epochs):
             perm = perms[e] if perms is not None else population_permutations(T, N, self.members, device=adv.device)
             for i in range(0, per_member, self.minibatch):
                 self.minibatch_step(obs_f, act_f, logp_f, adv_f, ret_f, perm, i, min(self.minibatch, per_member - i))
+            if self.diagnostics:   # what this epoch did to every member, and who still updates in the next one
+                self.diag.check(e + 1, obs_f.view(T, N, -1), act_f, logp_f, ret_f, self.val_b.contiguous(), self.flat, self.param_stride,
+                                self.n_params, self.arch, self.hyper, self._kl_limit())
         st = self.stats_buf.tolist()   # of every member's last minibatch
         log_std = [float(x) for x in self.flat[:, (self.n_params - 1) // 2].tolist()]
         ent = [x + 0.5 * (1.0 + math.log(2.0 * math.pi)) for x in log_std]
-        return {"pg": [-r[0] for r in st], "vf": [0.5 * r[1] for r in st], "entropy": ent, "clip_frac": [r[2] for r in st]}
+        out = {"pg": [-r[0] for r in st], "vf": [0.5 * r[1] for r in st], "entropy": ent, "clip_frac": [r[2] for r in st]}
+        if self.diagnostics:
+            out.update(self.diag.report(self.epochs))
+        return out
 
     def iterate(self):
         """collect() + update(); per-member lists of mean_step_reward, pg, vf, entropy, clip_frac and, with track_episodes, of

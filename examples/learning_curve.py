@@ -110,6 +110,9 @@ def main():
                     "epochs_run of that iteration's update")
     ap.add_argument("--target-kl", type=float, default=None, help="train with PPO(target_kl=...): the KL guard (implies --diagnostics)")
     ap.add_argument("--diag-rows", type=int, default=None, help="PPO(diag_rows=...): the checks read about this many of the horizon's rows")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="train with PPO(max_grad_norm=...): every curve point carries grad_norm, max_grad_norm_seen, clipped_steps and "
+                    "skipped_steps of that iteration's update")
     ap.add_argument("--episode-ledger", action="store_true",
                     help="train with PPO(track_episodes=True): true_mean_episode_return and episodes in every curve point, and the "
                     "held-out evaluation through pcc_rl_amd.evaluate (the library's episode ledger)")
@@ -117,7 +120,8 @@ def main():
     dev = torch.device("cuda:0")
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device=dev, seed=args.seed)
     agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs, track_episodes=args.episode_ledger,
-                normalize_reward=args.normalize_reward, diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows)
+                normalize_reward=args.normalize_reward, diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows,
+                max_grad_norm=args.max_grad_norm)
     untrained = {k: v.clone() for k, v in agent.policy.state_dict().items()}
     iters = max(1, int(round(args.env_steps / (args.envs * args.horizon))))
     curve = []
@@ -129,6 +133,8 @@ def main():
                       "entropy": s.get("entropy"), "value_loss": s.get("vf"), "wall_s": time.perf_counter() - t0})
         if agent.diagnostics:
             curve[-1].update({k: s[k] for k in ("approx_kl", "clip_fraction", "explained_variance", "max_log_ratio", "epochs_run")})
+        if agent.grad_clip is not None:
+            curve[-1].update({k: s[k] for k in ("grad_norm", "max_grad_norm_seen", "clipped_steps", "skipped_steps")})
         if args.episode_ledger:
             curve[-1].update(true_mean_episode_return=s["mean_episode_return"], episodes=s["episodes"])
     train_s = time.perf_counter() - t0
@@ -168,7 +174,7 @@ def main():
     out = {"what": "PPO (reference hyper-parameters, pi/vf MLP 32-16) on the MI355X simulator, then the trained controller against "
                    "baselines on held-out envs; python examples/learning_curve.py",
            "normalize_obs": bool(args.normalize_obs), "normalize_reward": bool(args.normalize_reward), "episode_ledger": bool(args.episode_ledger),
-           "diagnostics": bool(agent.diagnostics), "target_kl": args.target_kl, "diag_rows": args.diag_rows,
+           "diagnostics": bool(agent.diagnostics), "target_kl": args.target_kl, "diag_rows": args.diag_rows, "max_grad_norm": args.max_grad_norm,
            "training": {"envs": args.envs, "horizon": args.horizon, "iterations": iters, "env_steps": iters * args.envs * args.horizon,
                         "reference_budget_env_steps": 6 * 1600 * 410, "wall_s": train_s,
                         "env_steps_per_s_incl_learning": iters * args.envs * args.horizon / train_s,

@@ -63,6 +63,10 @@ def main():
                     help="stop updating a member for the rest of an update once its approximate KL exceeds 1.5 x this after an epoch, decided on "
                     "the device (implies --diagnostics)")
     ap.add_argument("--diag-rows", type=int, default=None, help="the checks read about this many of the horizon's rows (default: all)")
+    ap.add_argument("--max-grad-norm", default="",
+                    help="one limit, or one per member (comma-separated), on the global norm of every optimiser step's gradient; a member's "
+                    "step whose gradient is not finite is left out (PopulationPPO(max_grad_norm=...); 0: that guard alone).  The limit is a "
+                    "column of the hyper block: a replaced member takes its parent's in a --pbt-every generation")
     ap.add_argument("--export", default="", help="write every member's policy as TorchScript into <dir>/member<m> (export.export_policy)")
     ap.add_argument("--checkpoint", default="", help="write the whole training state here every --checkpoint-every iterations and at the end")
     ap.add_argument("--checkpoint-every", type=int, default=10)
@@ -89,7 +93,8 @@ def main():
                         gamma=values(args.gammas, 0.99),
                         seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None, normalize_obs=args.normalize_obs,
                         track_episodes=ledger, normalize_reward=args.normalize_reward,
-                        diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows)
+                        diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows,
+                        max_grad_norm=values(args.max_grad_norm, None) if args.max_grad_norm else None)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)
@@ -127,6 +132,12 @@ def main():
             curve.setdefault("true_mean_episode_return", []).append(s["mean_episode_return"])
             pbt = "  episodes: %s  true return: %s%s" % (" ".join("%d" % e for e in s["episodes"]),
                                                           " ".join("%7.1f" % r for r in s["mean_episode_return"]), pbt)
+        if pop.grad_clip is not None:
+            for key in ("grad_norm", "max_grad_norm_seen", "clipped_steps", "skipped_steps"):
+                curve.setdefault(key, []).append(s[key])
+            pbt = "  grad norm: %s  clipped: %s  skipped: %s%s" % (" ".join("%.3f" % g for g in s["grad_norm"]),
+                                                                   " ".join("%d" % n for n in s["clipped_steps"]),
+                                                                   " ".join("%d" % n for n in s["skipped_steps"]), pbt)
         if pop.diagnostics:
             for key in ("approx_kl", "clip_fraction", "explained_variance", "epochs_run"):
                 curve.setdefault(key, []).append(s[key])

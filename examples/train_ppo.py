@@ -40,6 +40,9 @@ def main():
                     help="stop updating the policy for the rest of an update once its approximate KL exceeds 1.5 x this after an epoch, decided on "
                     "the device (implies --diagnostics)")
     ap.add_argument("--diag-rows", type=int, default=None, help="the checks read about this many of the horizon's rows (default: all)")
+    ap.add_argument("--max-grad-norm", type=float, default=None,
+                    help="limit the global norm of every optimiser step's gradient to this, and leave out a step whose gradient is not finite, "
+                    "on the device (PPO(max_grad_norm=...); 0: that guard alone; stable-baselines3's default is 0.5)")
     ap.add_argument("--export", default="", help="write the trained policy here as TorchScript (export.export_policy)")
     ap.add_argument("--policy-in-step", action="store_true",
                     help="collect each horizon as one closed-loop call (pcc_rollout): the policy inside the env's launches")
@@ -54,7 +57,7 @@ def main():
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0, ring_pools=pools)
     agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
                 policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs, normalize_reward=args.normalize_reward,
-                diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows)
+                diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows, max_grad_norm=args.max_grad_norm)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)
@@ -74,6 +77,9 @@ def main():
         steps = (it + 1 - first) * args.envs * args.horizon
         diag = ("  kl %.4f  clipped %.3f  explained variance %6.3f  epochs %d"
                 % (s["approx_kl"], s["clip_fraction"], s["explained_variance"], s["epochs_run"])) if agent.diagnostics else ""
+        if agent.grad_clip is not None:
+            diag += "  grad norm %.3f (max %.3f)  clipped %d  skipped %d" % (s["grad_norm"], s["max_grad_norm_seen"], s["clipped_steps"],
+                                                                          s["skipped_steps"])
         print("iter %3d  env-steps %10d  reward/step %8.4f  entropy %6.3f  %.0f env-steps/s incl. learning%s"
               % (it, steps, s["mean_step_reward"], s["entropy"], steps / (time.perf_counter() - t0), diag))
     obs_norm = agent.obs_norm.member(0) if args.normalize_obs else None   # (shift, scale, clip): the policy is meaningless without it

@@ -73,7 +73,8 @@ int pcc_gae(const float *rewards, const float *values, const uint8_t *dones, con
  * 1 <= n_members <= 1024.  Parameter blocks (params, adam_m, adam_v, grad_out) are [n_members][param_stride] floats: each row
  * has the layout `params` has above in its first n_params floats; param_stride >= n_params and a multiple of 64 floats (every
  * member's block 256-byte aligned), anything else returns -1; the padding is never read or written.
- * hyper     caller-owned device floats [n_members][8]: {lr, clip, ent_coef, gamma, lam, 0, 0, 0}
+ * hyper     caller-owned device floats [n_members][8]: {lr, clip, ent_coef, gamma, lam, max_grad_norm, 0, 0}; column 5 is read
+ *           by pcc_ppo_minibatch_step_clip_pop alone (below), every other entry point carries it along unread
  *
  * pcc_policy_act_pop: pcc_policy_act for every member in ONE launch (the member is a grid dimension).  Every output is
  * bit-identical to n_members calls of pcc_policy_act on the members' row slices with params + m * param_stride: a member's
@@ -315,6 +316,46 @@ int pcc_update_diag_pop(const float *act, const float *logp_old, const float *me
 int pcc_update_diag(const float *act, const float *logp_old, const float *mean_new, const float *ret, const float *val, int T,
                     int row_step, int64_t n_envs, const float *params, int64_t log_std_index, float clip, double *diag,
                     double *scratch, void *stream);
+
+/*
+ * Gradient-norm clipping and a non-finite guard beside the fused PPO step: one optimiser step of every
+ * member as pcc_ppo_minibatch_step_pop takes it, with a global limit on the norm of each member's gradient and with a step whose
+ * gradient is not finite left out.  Every argument of pcc_ppo_minibatch_step_pop in its order and with its meaning, grad_out
+ * REQUIRED, then:
+ * hyper_grad   float32 [n_members][8] work block, caller-owned; it must not be `hyper`
+ * clip         float64 [n_members][clip_stride], clip_stride >= 8: row m is {sumsq, norm, c, state, steps, clipped_steps,
+ *              skipped_steps, max_norm_seen}.  Columns 0 - 3 are overwritten by every call; columns 4 - 7 are accumulated, the caller
+ *              zeroes them at the start of an update; the padding is never read or written
+ * Four launches on `stream`, nothing synchronizes, no atomics:
+ * 1. hyper_grad[m][0 .. 8) = hyper[m][0 .. 8) with hyper_grad[m][0] = 0.0f.
+ * 2. pcc_ppo_minibatch_step_pop with hyper_grad in place of hyper -- its two launches as they are; every member is gradient-only
+ *    there: grad_out holds the summed gradient G (the entropy term included) and stats_out what that call writes; params, adam_m and
+ *    adam_v are untouched.
+ * 3. Per member, n = n_params, g[p] = grad_out[m * param_stride + p]: 256 lanes; lane j adds (double)g[p] * (double)g[p] for p = j,
+ *    j + 256, j + 512, ... < n in increasing p, from 0.0, one float64 multiply and one float64 add per term, no contraction; then
+ *    the lane sums x[0 .. 256) are combined by the tree: for s = 128, 64, ..., 1: x[j] += x[j + s] for every j < s.  sumsq = x[0],
+ *    norm = sqrt(sumsq).  With lr = hyper[m][0] and M = hyper[m][5] -- `hyper` is the caller's block, which may be
+ *    pcc_update_diag_pop's hyper_live -- and c64 = (double)M / (norm + 1e-6), torch.nn.utils.clip_grad_norm_'s coefficient, the first
+ *    of these that holds gives the member's state:
+ *      lr == 0              state 3, gradient only: nothing but the row of clip is written
+ *      sumsq not finite     state 2, skipped: params, adam_m and adam_v of the member keep their bits
+ *      M > 0 && c64 < 1.0   state 1, clipped: c = (float)c64
+ *      otherwise            state 0: c = 1.0f                             (c is reported as 1 in the states 2 and 3)
+ *    In the states 0 and 1, for every p < n: gc = g[p] * c, one float32 multiply (c == 1.0f leaves g[p] exactly), then Adam on gc
+ *    operation for operation as pcc_ppo_minibatch_step_pop does it on g[p], the bias corrections computed on the host as there: a
+ *    step in state 0 leaves in params, adam_m and adam_v the bits pcc_ppo_minibatch_step_pop leaves.  Then steps += 1 in the states
+ *    0 and 1, clipped_steps += 1 in state 1, skipped_steps += 1 in state 2, max_norm_seen = fmax(max_norm_seen, norm): a NaN norm
+ *    does not enter it.  A member's results do not depend on the other members: they are bit-identical to the same call on that member
+ *    alone as a population of one.
+ * adam_step is the population's: it goes on for a skipped member as it does for a stopped one.
+ * Returns 0; -1, with nothing written and before any device call, for everything pcc_ppo_minibatch_step_pop answers -1 to, a NULL
+ * grad_out / hyper_grad / clip, hyper_grad == hyper, clip_stride < 8; -2 outside the domain of pcc_ppo_supported; -3 launch failure.
+ */
+int pcc_ppo_minibatch_step_clip_pop(const float *obs, const float *act, const float *logp_old, const float *adv, const float *ret,
+                                    const int64_t *perm, int64_t perm_stride, int64_t start, int64_t count, int obs_dim, int h1, int h2,
+                                    float *params, float *adam_m, float *adam_v, int64_t param_stride, int n_members, const float *hyper,
+                                    int adam_step, float beta1, float beta2, float eps, float *scratch, float *grad_out, float *stats_out,
+                                    float *hyper_grad, double *clip, int64_t clip_stride, void *stream);
 
 #ifdef __cplusplus
 }

@@ -52,7 +52,8 @@ SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params",
            "pcc_episode_scratch_doubles", "pcc_episode_update_pop", "pcc_episode_update",
            "pcc_return_scratch_doubles", "pcc_return_stats_update_pop", "pcc_reward_normalise_pop", "pcc_return_stats_update",
            "pcc_reward_normalise",
-           "pcc_policy_act_rows_pop", "pcc_update_diag_scratch_doubles", "pcc_update_diag_pop", "pcc_update_diag"]
+           "pcc_policy_act_rows_pop", "pcc_update_diag_scratch_doubles", "pcc_update_diag_pop", "pcc_update_diag",
+           "pcc_ppo_minibatch_step_clip_pop"]
 
 
 class PccError(RuntimeError):
@@ -181,6 +182,8 @@ def lib():
     L.pcc_update_diag_pop.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, i32, vp, i64, i64, vp, dbl, i32, vp, i64, vp, vp, vp, vp]
     L.pcc_update_diag.restype = i32
     L.pcc_update_diag.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, vp, i64, f32, vp, vp, vp]
+    L.pcc_ppo_minibatch_step_clip_pop.restype = i32   # (pcc_ppo_minibatch_step_pop's arguments, then hyper_grad, clip, clip_stride)
+    L.pcc_ppo_minibatch_step_clip_pop.argtypes = L.pcc_ppo_minibatch_step_pop.argtypes[:-1] + [vp, vp, i64, vp]
     L.pcc_debug_pass_stats.restype = i32
     L.pcc_debug_pass_stats.argtypes = [vp, vp, i32]
     L.pcc_debug_path_stats.restype = i32

@@ -24,7 +24,8 @@ library call per stage for all of them, and evolve() between generations.  What 
 _RolloutRows (the buffers of a rollout, the observation normaliser's place in it, the fused loop, and the hand-over of the reward
 and done rows to the episode ledger of track_episodes=True: DESIGN.md section 21, and to the reward normaliser of
 normalize_reward=True: section 22), _Trainer (the options -- among them the update diagnostics and the KL guard of
-diagnostics=True / target_kl: updiag.UpdateDiagnostics, section 23 --, the first observation, the
+diagnostics=True / target_kl: updiag.UpdateDiagnostics, section 23, and the limit on the gradient norm of max_grad_norm:
+gradclip.GradClip, section 24 --, the first observation, the
 checkpoint's common part) and native.call / native.current_stream.  They stay two classes: PPO draws its
 permutations with randperm and takes the last value from the torch module, and a merge would change its numbers.
 """
@@ -36,6 +37,7 @@ from torch import nn
 from .env import BatchedNetworkEnv, _ptr
 from .native import call, current_stream, lib
 from .episodes import EpisodeLedger
+from .gradclip import GradClip, limits as _grad_limits
 from .obsnorm import ObsNormalizer
 from .rewnorm import RewardNormalizer
 from .updiag import UpdateDiagnostics
@@ -315,6 +317,21 @@ class _Trainer(object):
         row_step = 1 if diag_rows is None else max(1, int(horizon) // int(diag_rows))
         self.diag = UpdateDiagnostics(int(env.n_envs), members, env.device, row_step)
 
+    def _set_grad_clip(self, env, max_grad_norm, fused_update=True, members=1):
+        """max_grad_norm: every optimiser step goes through pcc_ppo_minibatch_step_clip_pop with the members'
+        limits in column 5 of hyper; None: the steps are the unclipped entry points', as before.  The buffers (gradclip.GradClip)
+        are made once the parameter blocks are."""
+        who = type(self).__name__
+        self.max_grad_norm, self.grad_clip = None, None
+        if max_grad_norm is None:
+            return
+        self.max_grad_norm = _grad_limits(max_grad_norm, members, who)
+        if not fused_update:
+            raise ValueError("%s(max_grad_norm=...) needs the fused update (fused_update=True): the clipped step is a HIP kernel beside "
+                             "the fused step" % who)
+        if torch.device(env.device).type != "cuda":
+            raise ValueError("max_grad_norm runs HIP kernels: it needs the env on the GPU (device=%r); there is no CPU path" % (env.device,))
+
     def _kl_limit(self):
         """What pcc_update_diag_pop stops a member at: 1.5 x the target, as stable-baselines3 and Spinning Up do; 0: no guard."""
         return 0.0 if self.target_kl is None else 1.5 * self.target_kl
@@ -412,7 +429,7 @@ class PPO(_Trainer):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
                  epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
                  normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False, normalize_reward=False, clip_reward=10.0,
-                 diagnostics=False, target_kl=None, diag_rows=None):
+                 diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
         optimiser steps per epoch, thousands of launches of a few microseconds of work each.
@@ -433,7 +450,15 @@ class PPO(_Trainer):
         target_kl (implies diagnostics): once the approximate KL exceeds 1.5 x target_kl after an epoch -- or is NaN -- the later
         minibatches of this update are gradient-only (the parameters and Adam's moments stay; Adam's step count goes on), decided on
         the device without a synchronise.  diag_rows=R: the checks read every max(1, horizon // R)-th row.  Both need the fused
-        update."""
+        update.
+        max_grad_norm=M (>= 0): every optimiser step limits the global norm of its gradient to M, as torch.nn.utils.clip_grad_norm_
+        does, and a step whose gradient is not finite changes neither the parameters nor Adam's moments (Adam's step count goes on);
+        M = 0 is that guard alone.  One library call per step beside the fused step's kernels (gradclip.GradClip, self.grad_clip;
+        DESIGN.md section 24); update() adds grad_norm (the last step's), max_grad_norm_seen, clipped_steps and skipped_steps.  A
+        step that neither clips nor skips leaves the bits the unclipped step leaves.  Needs the fused update."""
+        self._set_grad_clip(env, max_grad_norm, fused_update)
+        if self.max_grad_norm is not None:
+            self.max_grad_norm = self.max_grad_norm[0]   # (one policy: a number, read at every update like lr: _hyper_now)
         if (diagnostics or target_kl is not None) and not fused_update:
             raise ValueError("PPO(diagnostics=True / target_kl) needs the fused update (fused_update=True): the framework path has no "
                              "diagnostics")
@@ -464,12 +489,15 @@ class PPO(_Trainer):
             self.adam_m, self.adam_v, self.adam_t = torch.zeros_like(self.flat), torch.zeros_like(self.flat), 0
             self.scratch = torch.empty(lib().pcc_ppo_scratch_floats(env.obs_dim, arch[0], arch[1]), device=env.device)
             self.stats_buf = torch.zeros(4, device=env.device)
-        elif self.diagnostics:
-            raise ValueError("PPO(diagnostics=True / target_kl) needs the fused update: the library has no pcc_ppo_minibatch_step for "
-                             "observation length %d, hidden %s" % (env.obs_dim, list(arch)))
-        if self.diagnostics:   # the [1][8] hyper block the checks read the clip range from, and the step of target_kl its lr
+        elif self.diagnostics or self.max_grad_norm is not None:
+            raise ValueError("PPO(diagnostics=True / target_kl / max_grad_norm) needs the fused update: the library has no "
+                             "pcc_ppo_minibatch_step for observation length %d, hidden %s" % (env.obs_dim, list(arch)))
+        if self.diagnostics or self.max_grad_norm is not None:
+            # the [1][8] hyper block the checks read the clip range from, the step of target_kl its lr, the clipped step its limit
             self.hyper = torch.zeros((1, HYPER_COLS), dtype=torch.float32, device=env.device)   # (filled at every update: _hyper_now)
             self.param_stride = (self.flat.numel() + 63) // 64 * 64   # (one member: the padding is never read or written)
+        if self.max_grad_norm is not None:
+            self.grad_clip = GradClip(self.param_stride, 1, env.device)
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=lr, eps=self.adam_eps)
         self._first_obs(1, clip_obs, norm_eps)
         if self.minibatch is None:
@@ -612,9 +640,10 @@ class PPO(_Trainer):
              _ptr(grad_out), _ptr(self.stats_buf), current_stream(obs_f.device))
 
     def _hyper_now(self):
-        """self.hyper from lr, clip, ent_coef, gamma and lam as they are NOW: a caller may change them between updates (a schedule),
-        and the guarded step and the checks must see what minibatch_step_fused would pass."""
-        row = [[self.lr, self.clip, self.ent_coef, self.gamma, self.lam] + [0.0] * (HYPER_COLS - len(HYPER_NAMES))]
+        """self.hyper from lr, clip, ent_coef, gamma, lam and the limit on the gradient norm as they are NOW: a caller may change them
+        between updates (a schedule), and the guarded step and the checks must see what minibatch_step_fused would pass."""
+        limit = 0.0 if self.max_grad_norm is None else _grad_limits(self.max_grad_norm, 1, "PPO")[0]
+        row = [[self.lr, self.clip, self.ent_coef, self.gamma, self.lam, limit] + [0.0] * (HYPER_COLS - len(HYPER_NAMES))]
         self.hyper.copy_(torch.tensor(row, dtype=torch.float32))
         return self.hyper
 
@@ -630,13 +659,32 @@ class PPO(_Trainer):
              _ptr(self.diag.hyper_live), max(self.adam_t, 1), 0.9, 0.999, self.adam_eps, _ptr(self.scratch), None, _ptr(self.stats_buf),
              current_stream(obs_f.device))
 
+    def _minibatch_step_clipped(self, obs_f, act_f, logp_f, adv_f, ret_f, perm, start, count):
+        """The step under max_grad_norm: pcc_ppo_minibatch_step_clip_pop with ONE member -- the fused step's two launches as a
+        gradient-only call, then the norm, the coefficient and Adam on the scaled gradient.  Its hyper block
+        is self.hyper, or under target_kl the checks' hyper_live: a stopped member stays gradient-only."""
+        if self.lr != 0.0:   # (as minibatch_step_fused: a gradient-only step is no step of Adam's)
+            self.adam_t += 1
+        h1, h2 = self.policy.hidden
+        gc = self.grad_clip
+        call("pcc_ppo_minibatch_step_clip_pop", _ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), perm.numel(),
+             start, count, obs_f.shape[1], h1, h2, _ptr(self.flat), _ptr(self.adam_m), _ptr(self.adam_v), self.param_stride, 1,
+             _ptr(self.hyper if self.target_kl is None else self.diag.hyper_live), max(self.adam_t, 1), 0.9, 0.999, self.adam_eps,
+             _ptr(self.scratch), _ptr(gc.grad), _ptr(self.stats_buf), _ptr(gc.hyper_grad), _ptr(gc.clip), gc.clip.stride(0),
+             current_stream(obs_f.device))
+
     def _update_fused(self, obs_f, act_f, logp_f, adv_f, ret_f, T=None):
         n = obs_f.shape[0]
         obs_f, act_f = obs_f.contiguous(), act_f.reshape(n).contiguous()
         logp_f, adv_f, ret_f = logp_f.contiguous(), adv_f.contiguous(), ret_f.contiguous()
         step = self.minibatch_step_fused if self.target_kl is None else self._minibatch_step_guarded
+        if self.diagnostics or self.grad_clip is not None:
+            self._hyper_now()
+        if self.grad_clip is not None:
+            step = self._minibatch_step_clipped
+            self.grad_clip.begin()
         if self.diagnostics:
-            self.diag.begin(self._hyper_now())
+            self.diag.begin(self.hyper)
         for e in range(self.epochs):
             perm = torch.randperm(n, device=obs_f.device)
             for i in range(0, n, self.minibatch):
@@ -649,6 +697,8 @@ class PPO(_Trainer):
         out = {"pg": -st[0], "vf": 0.5 * st[1], "entropy": ent, "clip_frac": st[2]}
         if self.diagnostics:
             out.update({k: v[0] for k, v in self.diag.report(self.epochs).items()})
+        if self.grad_clip is not None:
+            out.update({k: v[0] for k, v in self.grad_clip.report().items()})
         return out
 
     def state_dict(self):
@@ -722,13 +772,13 @@ def normalise_per_member(adv, n_members):
     return out
 
 
-HYPER_COLS = 8   # a row of `hyper` (include/pcc_policy.h): {lr, clip, ent_coef, gamma, lam, 0, 0, 0}
-HYPER_NAMES = ("lr", "clip", "ent_coef", "gamma", "lam")   # the columns PopulationPPO.evolve can perturb or bound, by name
+HYPER_COLS = 8   # a row of `hyper` (include/pcc_policy.h): {lr, clip, ent_coef, gamma, lam, max_grad_norm, 0, 0}
+HYPER_NAMES = ("lr", "clip", "ent_coef", "gamma", "lam", "max_grad_norm")   # the columns PopulationPPO.evolve can perturb or bound, by name
 
 
 def explore_matrix(factors=(0.8, 1.2), explore=("lr", "ent_coef"), bounds=None):
     """The [8][4] rows {factor_lo, factor_hi, min, max} pcc_pbt_evolve takes (include/pcc_policy.h), as a list: the columns
-    named in `explore` get `factors`, every other column -- the three reserved ones too -- {1, 1, -inf, +inf}, which inherits
+    named in `explore` get `factors`, every other column -- the two reserved ones too -- {1, 1, -inf, +inf}, which inherits
     the parent's value unchanged; bounds: {name: (lo, hi)}."""
     inf = float("inf")
     rows = [[1.0, 1.0, -inf, inf] for _ in range(HYPER_COLS)]
@@ -745,7 +795,7 @@ def explore_matrix(factors=(0.8, 1.2), explore=("lr", "ent_coef"), bounds=None):
 
 
 def _hyper_columns(members, **named):
-    """lr, clip, ent_coef, gamma, lam -- each a scalar (a number, a numpy scalar, a 0-dim tensor) or one value per member -- as
+    """lr, clip, ent_coef, gamma, lam, max_grad_norm -- each a scalar (a number, a numpy scalar, a 0-dim tensor) or one value per member -- as
     `members` rows of `hyper`."""
     cols = []
     for name in HYPER_NAMES:
@@ -774,20 +824,26 @@ class PopulationPPO(_Trainer):
     KL after an epoch exceeds 1.5 x target_kl, or is NaN (its parameters have gone non-finite), is stopped for the rest of that
     update: its later minibatches are gradient-only, exactly as an lr == 0 member's are -- its parameters and Adam's moments stay as
     they are -- while the other members go on; Adam's step count stays the population's (it goes on for the stopped member too).  The
-    decision is the kernel's: no copy to the host, no synchronise."""
+    decision is the kernel's: no copy to the host, no synchronise.
+    max_grad_norm: PPO's option, a scalar or one limit per member: column 5 of hyper, so a replaced member
+    takes its parent's through evolve(), which can perturb or bound it by its name; update() adds per-member lists of grad_norm,
+    max_grad_norm_seen, clipped_steps and skipped_steps.  A member whose gradient is not finite skips that step alone; the others
+    go on.  None (the default): column 5 stays 0 and the steps are pcc_ppo_minibatch_step_pop's."""
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
                  epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False,
-                 normalize_reward=False, clip_reward=10.0, diagnostics=False, target_kl=None, diag_rows=None):
+                 normalize_reward=False, clip_reward=10.0, diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None):
         members = int(members)
         self._set_normalize(env, normalize_obs)
         if members < 1 or members > 1024:
             raise ValueError("PopulationPPO: members = %d (1 .. 1024)" % members)
+        self._set_grad_clip(env, max_grad_norm, True, members)
         if len(arch) != 2:
             raise ValueError("PopulationPPO needs a policy of two hidden layers (arch = %r)" % (tuple(arch),))
         if int(env.n_envs) % members != 0:
             raise ValueError("PopulationPPO: %d envs do not divide into %d members" % (env.n_envs, members))
-        self.hyper_rows = _hyper_columns(members, lr=lr, clip=clip, ent_coef=ent_coef, gamma=gamma, lam=lam)
+        self.hyper_rows = _hyper_columns(members, lr=lr, clip=clip, ent_coef=ent_coef, gamma=gamma, lam=lam,
+                                         max_grad_norm=0.0 if max_grad_norm is None else self.max_grad_norm)
         seeds = list(range(members)) if seeds is None else [int(x) for x in seeds]
         if len(seeds) != members:
             raise ValueError("PopulationPPO: seeds has %d values for %d members" % (len(seeds), members))
@@ -819,6 +875,8 @@ class PopulationPPO(_Trainer):
         self.scratch_floats = lib().pcc_ppo_scratch_floats(D, *self.arch)
         self.scratch = torch.empty(members * self.scratch_floats, device=dev)
         self.stats_buf = torch.zeros((members, 4), device=dev)
+        if self.max_grad_norm is not None:
+            self.grad_clip = GradClip(self.param_stride, members, dev)
         self._first_obs(members, clip_obs, norm_eps)
         per_member = self.n_member * horizon
         self.minibatch = min(per_member, max(2048, per_member // 4)) if minibatch is None else int(minibatch)
@@ -871,6 +929,14 @@ class PopulationPPO(_Trainer):
             raise ValueError("minibatch [%d, %d) outside a member's rollout" % (start, start + count))
         self.adam_t += 1
         D = obs_f.shape[1]
+        if self.grad_clip is not None:   # the same step through the clipped entry: the limits are column 5 of the hyper block
+            gc = self.grad_clip
+            return call("pcc_ppo_minibatch_step_clip_pop", _ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm),
+                        perm.stride(0), start, count, D, self.arch[0], self.arch[1], _ptr(self.flat), _ptr(self.adam_m),
+                        _ptr(self.adam_v), self.param_stride, self.members,
+                        _ptr(self.hyper if self.target_kl is None else self.diag.hyper_live), self.adam_t, 0.9, 0.999, self.adam_eps,
+                        _ptr(self.scratch), _ptr(gc.grad if grad_out is None else grad_out), _ptr(self.stats_buf), _ptr(gc.hyper_grad),
+                        _ptr(gc.clip), gc.clip.stride(0), self._stream())
         call("pcc_ppo_minibatch_step_pop", _ptr(obs_f), _ptr(act_f), _ptr(logp_f), _ptr(adv_f), _ptr(ret_f), _ptr(perm), perm.stride(0),
              start, count, D, self.arch[0], self.arch[1], _ptr(self.flat), _ptr(self.adam_m),
              _ptr(self.adam_v), self.param_stride, self.members,
@@ -889,6 +955,8 @@ class PopulationPPO(_Trainer):
         per_member = T * self.n_member
         if self.diagnostics:
             self.diag.begin(self.hyper)
+        if self.grad_clip is not None:
+            self.grad_clip.begin()
         for e in range(self.epochs):
             perm = perms[e] if perms is not None else population_permutations(T, N, self.members, device=adv.device)
             for i in range(0, per_member, self.minibatch):
@@ -902,6 +970,8 @@ class PopulationPPO(_Trainer):
         out = {"pg": [-r[0] for r in st], "vf": [0.5 * r[1] for r in st], "entropy": ent, "clip_frac": [r[2] for r in st]}
         if self.diagnostics:
             out.update(self.diag.report(self.epochs))
+        if self.grad_clip is not None:
+            out.update(self.grad_clip.report())
         return out
 
     def iterate(self):

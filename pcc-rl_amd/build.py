@@ -152,9 +152,11 @@ def build_info(lib=None):
 
 
 def build_variants(force=False, verbose=False):
-    """The variant libraries of VARIANTS (see there) and the test harness of rtt_means; returns {name: path} of the variants."""
+    """The variant libraries of VARIANTS (see there) and the test harnesses of rtt_means and of the boundary searches; returns
+    {name: path} of the variants."""
     out = {name: build_library(force=force, verbose=verbose, extra_flags=flags, out=variant_path(name)) for name, flags in VARIANTS.items()}
     build_rtt_harness(force=force, verbose=verbose)
+    build_search_harness(force=force, verbose=verbose)
     return out
 
 
@@ -165,19 +167,33 @@ RTT_HARNESS_SRC = os.path.join(ROOT, "tests", "kernels", "rtt_means_harness.hip"
 RTT_HARNESS_LIB = os.path.join(LIB_DIR, "libpcc_rtt_harness.so")
 
 
+# tests/kernels/retire_search_harness.hip: search_many, search_boundary, fix_drop_boundary_g and drop_hop1_candidate_g of
+# csrc/pcc_retire_env.h, 8 and 16 lanes, behind four C entries, for tests/test_retire_search.py.  Built as the rtt harness is.
+SEARCH_HARNESS_SRC = os.path.join(ROOT, "tests", "kernels", "retire_search_harness.hip")
+SEARCH_HARNESS_LIB = os.path.join(LIB_DIR, "libpcc_search_harness.so")
+
+
 def build_rtt_harness(force=False, verbose=False):
     """Compile the harness if it is missing or older than its source or the headers; returns its path -- None, and nothing is
     built, in a tree that has no tests/ (the harness is test infrastructure: the product builds without it)."""
-    lib = RTT_HARNESS_LIB
-    if not os.path.exists(RTT_HARNESS_SRC):
+    return _build_harness(RTT_HARNESS_SRC, RTT_HARNESS_LIB, force, verbose)
+
+
+def build_search_harness(force=False, verbose=False):
+    """The same for the harness of the boundary searches and the near-group repairs."""
+    return _build_harness(SEARCH_HARNESS_SRC, SEARCH_HARNESS_LIB, force, verbose)
+
+
+def _build_harness(src, lib, force, verbose):
+    if not os.path.exists(src):
         return None
-    if not force and os.path.exists(lib) and os.path.getmtime(lib) >= max(os.path.getmtime(p) for p in [RTT_HARNESS_SRC] + HEADERS):
+    if not force and os.path.exists(lib) and os.path.getmtime(lib) >= max(os.path.getmtime(p) for p in [src] + HEADERS):
         return lib
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     if not os.path.exists(hipcc):
         raise RuntimeError("hipcc not found; cannot build %s" % lib)
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [hipcc] + HIPCC_FLAGS + ["-I", INCLUDE, "-I", CSRC, "-shared", RTT_HARNESS_SRC, "-o", lib]
+    cmd = [hipcc] + HIPCC_FLAGS + ["-I", INCLUDE, "-I", CSRC, "-shared", src, "-o", lib]
     if verbose:
         print(" ".join(cmd))
     p = subprocess.run(cmd, stderr=subprocess.PIPE, universal_newlines=True)

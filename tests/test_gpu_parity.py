@@ -527,7 +527,9 @@ def test_long_drop_runs_match_oracle(params, wide):
     orders such near groups exactly around its boundaries (fix_drop_boundary_g / drop_hop1_candidate_g: a group of 8 or 16
     lanes looks at a window of records at a time, the lead lane walks windows longer than the group).  Every env retired
     by 16 lanes (wide = 0) and every env by 8 (1e9); windows shorter and longer than either; ns:111, 141-146, 161, 178
-    (the heap orders equal times by latency, then by the dropped flag)."""
+    (the heap orders equal times by latency, then by the dropped flag).  How often these runs reach a window longer than the
+    group, one at the ring's head or tail, or a cut at a given place of a group is not counted here: tests/test_retire_search.py
+    holds the same routines to linear scans on a table that has every such case by construction."""
     n_envs, n_steps = 192, 70
     rs = np.random.RandomState(21)
     acts = rs.uniform(-0.5, 1.5, (n_envs, n_steps))

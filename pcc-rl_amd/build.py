@@ -152,11 +152,12 @@ def build_info(lib=None):
 
 
 def build_variants(force=False, verbose=False):
-    """The variant libraries of VARIANTS (see there) and the test harnesses of rtt_means and of the boundary searches; returns
+    """The variant libraries of VARIANTS (see there) and the test harnesses of rtt_means, of the boundary searches and of the send half's wave passes; returns
     {name: path} of the variants."""
     out = {name: build_library(force=force, verbose=verbose, extra_flags=flags, out=variant_path(name)) for name, flags in VARIANTS.items()}
     build_rtt_harness(force=force, verbose=verbose)
     build_search_harness(force=force, verbose=verbose)
+    build_send_harness(force=force, verbose=verbose)
     return out
 
 
@@ -184,7 +185,23 @@ def build_search_harness(force=False, verbose=False):
     return _build_harness(SEARCH_HARNESS_SRC, SEARCH_HARNESS_LIB, force, verbose)
 
 
-def _build_harness(src, lib, force, verbose):
+# tests/kernels/send_pass_harness.hip: heavy_mi (a wavefront, staged or not, and a team) and heavy_mi2 (staged or not) of
+# csrc/pcc_wave_pass.h, TRACE and Philox, behind two C entries, for tests/test_send_pass_device.py.  Built twice with the
+# product's flags: plainly, and with -DPCC_PROFILE=1 (the passes count themselves by regime: what the test's reach check reads).
+SEND_HARNESS_SRC = os.path.join(ROOT, "tests", "kernels", "send_pass_harness.hip")
+SEND_HARNESS_LIB = os.path.join(LIB_DIR, "libpcc_send_harness.so")
+SEND_HARNESS_PROF_LIB = os.path.join(LIB_DIR, "libpcc_send_harness_prof.so")
+
+
+def build_send_harness(force=False, verbose=False):
+    """The same for the harness of the send half's wave passes; returns (plain, profile) paths, or None without tests/."""
+    plain = _build_harness(SEND_HARNESS_SRC, SEND_HARNESS_LIB, force, verbose)
+    if plain is None:
+        return None
+    return plain, _build_harness(SEND_HARNESS_SRC, SEND_HARNESS_PROF_LIB, force, verbose, extra_flags=("-DPCC_PROFILE=1",))
+
+
+def _build_harness(src, lib, force, verbose, extra_flags=()):
     if not os.path.exists(src):
         return None
     if not force and os.path.exists(lib) and os.path.getmtime(lib) >= max(os.path.getmtime(p) for p in [src] + HEADERS):
@@ -193,7 +210,7 @@ def _build_harness(src, lib, force, verbose):
     if not os.path.exists(hipcc):
         raise RuntimeError("hipcc not found; cannot build %s" % lib)
     os.makedirs(LIB_DIR, exist_ok=True)
-    cmd = [hipcc] + HIPCC_FLAGS + ["-I", INCLUDE, "-I", CSRC, "-shared", src, "-o", lib]
+    cmd = [hipcc] + HIPCC_FLAGS + list(extra_flags) + ["-I", INCLUDE, "-I", CSRC, "-shared", src, "-o", lib]
     if verbose:
         print(" ".join(cmd))
     p = subprocess.run(cmd, stderr=subprocess.PIPE, universal_newlines=True)

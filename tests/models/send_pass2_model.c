@@ -453,6 +453,49 @@ static int sweep64_pass(st2_t *st, const double gap[2], double end, double dl, d
     return 1;
 }
 
+/* one fuzzed link, pair of senders and interval: the generators of pcc_model2_fuzz_sweeps (see there), kind 0 .. 3 */
+typedef struct { int kind; double ebw, maxq, dl, lr, now, end, rate[2], gap[2]; st2_t s0; } gen2_t;
+static void gen2_sweeps(gen2_t *g) {
+    const double bw = 100.0 + 400.0 * fz_unit();
+    const double ebw = 1.0 / bw;
+    const int kind = (int)(fz_next() % 4u);   /* 0, 1: the generators of pcc_model2_fuzz; 2: (a); 3: (b) */
+    double queue = 1.0 + floor(exp(8.0 * fz_unit()));
+    if (fz_unit() < 0.35) {   /* queue limits around powers of two (in seconds) */
+        const double B = pow2((int)(fz_next() % 8) - 3);
+        queue = floor(B * bw + 6.0 * fz_unit() - 3.0);
+        if (queue < 2.0) queue = 2.0;
+    }
+    if (kind == 3) queue = 2000.0 + floor(1000.0 * fz_unit());
+    const double maxq = queue / bw;
+    const double dl = 0.05 + 0.45 * fz_unit();
+    double lr = fz_unit() < 0.25 ? 0.0 : 0.05 * fz_unit();
+    double load = fz_unit() < 0.7 ? 1.02 + 0.8 * fz_unit() : 0.4 + 1.2 * fz_unit();
+    double share = 0.2 + 0.6 * fz_unit();
+    if (kind == 2) { load = 0.3 + 0.65 * fz_unit(); if (fz_unit() < 0.5) share = 0.5; }
+    if (kind == 3) { load = 1.2 + 0.4 * fz_unit(); lr = 0.0; }
+    double rate[2] = {bw * load * share, bw * load * (1.0 - share)};
+    for (int s = 0; s < 2; s++) { if (rate[s] < 40.0) rate[s] = 40.0; if (rate[s] > 1000.0) rate[s] = 1000.0; }
+    const double gap[2] = {1.0 / rate[0], 1.0 / rate[1]};
+    double now = fz_unit() < 0.2 ? 0.05 + 3.0 * fz_unit() : 3.0 + 400.0 * fz_unit();
+    if (kind == 3 && fz_unit() < 0.5) {   /* old enough for 64 positions, too young for 256 */
+        const double gmax = gap[0] > gap[1] ? gap[0] : gap[1];
+        now = gmax * (130.0 + 120.0 * fz_unit());
+    }
+    st2_t s0;
+    s0.tu = now - ebw * fz_unit();
+    s0.q = fz_unit() < 0.2 ? maxq * fz_unit() : (fz_unit() < 0.5 ? maxq - ebw * 3.0 * fz_unit() : maxq * (0.5 + 0.5 * fz_unit()));
+    if (kind == 2) s0.q = fz_unit() < 0.5 ? 0.0 : ebw * 2.0 * fz_unit();
+    if (kind == 3) s0.q = maxq * (0.4 + 0.2 * fz_unit());
+    if (s0.q < 0.0) s0.q = 0.0;
+    s0.t[0] = now + gap[0] * fz_unit();
+    s0.t[1] = now + gap[1] * fz_unit();
+    if (fz_unit() < 0.1 || (kind == 2 && fz_unit() < 0.5)) s0.t[1] = s0.t[0];   /* equal times: sender 0 first */
+    s0.a[0] = s0.a[1] = s0.d[0] = s0.d[1] = 0;
+    const double end = now + (0.05 + 2.0 * fz_unit());
+    g->kind = kind; g->ebw = ebw; g->maxq = maxq; g->dl = dl; g->lr = lr; g->now = now; g->end = end;
+    g->rate[0] = rate[0]; g->rate[1] = rate[1]; g->gap[0] = gap[0]; g->gap[1] = gap[1]; g->s0 = s0;
+}
+
 /* n_cases random link states and intervals through heavy_mi2's choice of passes -- the token pass where its preconditions
  * hold (use_token != 0; after a short one the next three passes go by sweeps), else the 256-position sweep pass, else the
  * 64-lane sweep pass, else the plain recurrence -- against the plain recurrence alone; returns the number of mismatching cases.
@@ -473,42 +516,12 @@ long pcc_model2_fuzz_sweeps(long n_cases, uint64_t seed, int use_token, uint64_t
     g_lanes = 64; g_per_lane = 4;   /* the kernel's token pass: 256 positions */
     for (int k = 0; k < 14; k++) stats[k] = 0;
     for (long cs = 0; cs < n_cases; cs++) {
-        const double bw = 100.0 + 400.0 * fz_unit();
-        const double ebw = 1.0 / bw;
-        const int kind = (int)(fz_next() % 4u);   /* 0, 1: the generators of pcc_model2_fuzz; 2: (a); 3: (b) */
-        double queue = 1.0 + floor(exp(8.0 * fz_unit()));
-        if (fz_unit() < 0.35) {   /* queue limits around powers of two (in seconds) */
-            const double B = pow2((int)(fz_next() % 8) - 3);
-            queue = floor(B * bw + 6.0 * fz_unit() - 3.0);
-            if (queue < 2.0) queue = 2.0;
-        }
-        if (kind == 3) queue = 2000.0 + floor(1000.0 * fz_unit());
-        const double maxq = queue / bw;
-        const double dl = 0.05 + 0.45 * fz_unit();
-        double lr = fz_unit() < 0.25 ? 0.0 : 0.05 * fz_unit();
-        double load = fz_unit() < 0.7 ? 1.02 + 0.8 * fz_unit() : 0.4 + 1.2 * fz_unit();
-        double share = 0.2 + 0.6 * fz_unit();
-        if (kind == 2) { load = 0.3 + 0.65 * fz_unit(); if (fz_unit() < 0.5) share = 0.5; }
-        if (kind == 3) { load = 1.2 + 0.4 * fz_unit(); lr = 0.0; }
-        double rate[2] = {bw * load * share, bw * load * (1.0 - share)};
-        for (int s = 0; s < 2; s++) { if (rate[s] < 40.0) rate[s] = 40.0; if (rate[s] > 1000.0) rate[s] = 1000.0; }
-        const double gap[2] = {1.0 / rate[0], 1.0 / rate[1]};
-        double now = fz_unit() < 0.2 ? 0.05 + 3.0 * fz_unit() : 3.0 + 400.0 * fz_unit();
-        if (kind == 3 && fz_unit() < 0.5) {   /* old enough for 64 positions, too young for 256 */
-            const double gmax = gap[0] > gap[1] ? gap[0] : gap[1];
-            now = gmax * (130.0 + 120.0 * fz_unit());
-        }
-        st2_t s0;
-        s0.tu = now - ebw * fz_unit();
-        s0.q = fz_unit() < 0.2 ? maxq * fz_unit() : (fz_unit() < 0.5 ? maxq - ebw * 3.0 * fz_unit() : maxq * (0.5 + 0.5 * fz_unit()));
-        if (kind == 2) s0.q = fz_unit() < 0.5 ? 0.0 : ebw * 2.0 * fz_unit();
-        if (kind == 3) s0.q = maxq * (0.4 + 0.2 * fz_unit());
-        if (s0.q < 0.0) s0.q = 0.0;
-        s0.t[0] = now + gap[0] * fz_unit();
-        s0.t[1] = now + gap[1] * fz_unit();
-        if (fz_unit() < 0.1 || (kind == 2 && fz_unit() < 0.5)) s0.t[1] = s0.t[0];   /* equal times: sender 0 first */
-        s0.a[0] = s0.a[1] = s0.d[0] = s0.d[1] = 0;
-        const double end = now + (0.05 + 2.0 * fz_unit());
+        gen2_t g2;
+        gen2_sweeps(&g2);
+        const int kind = g2.kind;
+        const double ebw = g2.ebw, maxq = g2.maxq, dl = g2.dl, lr = g2.lr, now = g2.now, end = g2.end;
+        const double rate[2] = {g2.rate[0], g2.rate[1]}, gap[2] = {g2.gap[0], g2.gap[1]};
+        const st2_t s0 = g2.s0;
         for (int k = 0; k < MAXPK + 8192; k++) loss[k] = fz_unit() < lr;
         if ((rate[0] + rate[1]) * (end - now) > (double)MAXPK - 100.0) continue;
         stats[12] += kind == 2;
@@ -560,4 +573,117 @@ long pcc_model2_fuzz_sweeps(long n_cases, uint64_t seed, int use_token, uint64_t
     }
     g_lanes = lanes0; g_per_lane = per0;
     return bad;
+}
+
+/* ======================================================================================================================
+ * Entries for the case tables of tests/models/send_pass_cases.py (the device tests of heavy_mi2, tests/test_send_pass_device.py):
+ * cases go in and out as arrays, nothing here asserts.
+ * ====================================================================================================================== */
+typedef struct { double q, tu, t[2], dl, lr, maxq, ebw, gap[2], end; uint32_t sent[2]; } mcase2_t;   /* 96 bytes */
+
+/* (a) n cases of the generators of pcc_model2_fuzz_sweeps: kind 0 .. 3 as drawn (kind_only < 0) or only the cases of one kind
+ * (2: the link keeps running empty, 3: one busy period over the pass); both senders' intervals cut to max_packets packets each.
+ * kinds_out[c]: the kind of case c. */
+long pcc_cases2_fuzz(long n, uint64_t seed, int kind_only, double max_packets, mcase2_t *out, int32_t *kinds_out) {
+    fz = seed ? seed : 1;
+    long c = 0, guard = 0;
+    while (c < n && guard++ < 100 * n + 1000) {
+        gen2_t g;
+        gen2_sweeps(&g);
+        if (kind_only >= 0 && g.kind != kind_only) continue;
+        double end = g.end;
+        for (int s = 0; s < 2; s++)
+            if ((end - g.s0.t[s]) / g.gap[s] > max_packets) end = g.s0.t[s] + max_packets * g.gap[s];
+        mcase2_t *o = &out[c];
+        o->q = g.s0.q; o->tu = g.s0.tu; o->dl = g.dl; o->lr = g.lr; o->maxq = g.maxq; o->ebw = g.ebw; o->end = end;
+        for (int s = 0; s < 2; s++) { o->t[s] = g.s0.t[s]; o->gap[s] = g.gap[s]; o->sent[s] = 0; }
+        o->sent[0] = (uint32_t)(fz_next() & 3u);   /* Philox block alignment of a take-over */
+        if (kinds_out) kinds_out[c] = g.kind;
+        c++;
+    }
+    return c;
+}
+
+static long case2_packets(const mcase2_t *c, long room) {
+    long k = 0;
+    for (int s = 0; s < 2; s++) {
+        double t = c->t[s];
+        if (!(c->gap[s] > 0.0) || !(t + c->gap[s] > t)) return -1;
+        while (t < c->end) {
+            if (++k > room) return -1;
+            t += c->gap[s];
+        }
+    }
+    return k;
+}
+
+/* (b) the plain merged recurrence (plain) on n cases.  Case c owns the elements [off[c], off[c + 1]) of loss (loss[off[c] + k]:
+ * the k-th packet of the merged stream is lost at random) and of the four record arrays (sender x accepted / dropped, each in
+ * send order).  out[c]: the final state, a / d counted from 0.  Returns 0, or -(c + 1) for the first case that does not fit. */
+long pcc_cases2_plain(long n, const mcase2_t *cs, const uint8_t *loss, const int64_t *off, st2_t *out, rec_t *acc0, rec_t *drp0,
+                      rec_t *acc1, rec_t *drp1) {
+    for (long c = 0; c < n; c++) {
+        if (case2_packets(&cs[c], (long)(off[c + 1] - off[c])) < 0) return -(c + 1);
+        st2_t s;
+        memset(&s, 0, sizeof s);
+        s.q = cs[c].q; s.tu = cs[c].tu; s.t[0] = cs[c].t[0]; s.t[1] = cs[c].t[1];
+        rec_t *acc[2] = {acc0 + off[c], acc1 + off[c]}, *drp[2] = {drp0 + off[c], drp1 + off[c]};
+        plain(&s, cs[c].gap, cs[c].end, cs[c].dl, cs[c].maxq, cs[c].ebw, loss + off[c], 0, 1u << 30, acc, drp);
+        out[c] = s;
+    }
+    return 0;
+}
+
+#define MIRROR2_COLS 8
+/* (c) the mirror: heavy_mi2's choice of passes as pcc_model2_fuzz_sweeps drives it (the token pass on whole Philox blocks, then
+ * the 256-position sweep pass, the 64-lane sweep pass, the plain recurrence).  counts[c][MIRROR2_COLS]: passes / packets of the
+ * token pass (0, 1), the 256-position sweeps (2, 3), the 64-lane sweeps (4, 5), the plain recurrence (6, 7). */
+long pcc_cases2_mirror(long n, const mcase2_t *cs, const uint8_t *loss, const int64_t *off, st2_t *out, rec_t *acc0, rec_t *drp0,
+                       rec_t *acc1, rec_t *drp1, uint64_t *counts) {
+    const int lanes0 = g_lanes, per0 = g_per_lane;
+    g_lanes = 64; g_per_lane = 4;
+    long rc = 0;
+    for (long c = 0; c < n; c++) {
+        if (case2_packets(&cs[c], (long)(off[c + 1] - off[c])) < 0) { rc = -(c + 1); break; }
+        const mcase2_t *C = &cs[c];
+        st2_t md;
+        memset(&md, 0, sizeof md);
+        md.q = C->q; md.tu = C->tu; md.t[0] = C->t[0]; md.t[1] = C->t[1];
+        rec_t *macc[2] = {acc0 + off[c], acc1 + off[c]}, *mdrp[2] = {drp0 + off[c], drp1 + off[c]};
+        const uint32_t base = C->sent[0] + C->sent[1];            /* packets of the interval sent before the case begins */
+        const uint8_t *ls = loss + off[c] - base;                 /* ls[packet index of the interval] */
+        uint64_t *k = counts + c * MIRROR2_COLS;
+        for (int i = 0; i < MIRROR2_COLS; i++) k[i] = 0;
+        uint32_t km = base, chain_left = 0, guard = 0;
+        while ((md.t[0] < md.t[1] ? md.t[0] : md.t[1]) < C->end) {
+            if (++guard > 100000u) { rc = -(c + 1); break; }
+            uint32_t m = 0, early = 0;
+            const int held = chain_left != 0u;
+            if (chain_left) chain_left--;
+            if (!held && (km & 3u) == 0u) {
+                m = token_pass(&md, C->gap, C->end, C->dl, C->maxq, C->ebw, ls, km, macc, mdrp, &early);
+                if (m) { k[0]++; k[1] += m; }
+                if (m && early && m < 32u) chain_left = 3;
+            }
+            sweep_out_t so;
+            if (!m && sweep256_pass(&md, C->gap, C->end, C->dl, C->maxq, C->ebw, ls, km, macc, mdrp, &so)) {
+                m = so.committed;
+                if (m) { k[2]++; k[3] += m; }
+            }
+            if (!m && sweep64_pass(&md, C->gap, C->end, C->dl, C->maxq, C->ebw, ls, km, macc, mdrp, &so)) {
+                m = so.committed;
+                k[4]++; k[5] += m;
+                if (!m) { rc = -(c + 1); break; }
+            }
+            if (!m) {
+                m = plain(&md, C->gap, C->end, C->dl, C->maxq, C->ebw, ls, km, 64, macc, mdrp);
+                k[6]++; k[7] += m;
+            }
+            km += m;
+        }
+        if (rc) break;
+        out[c] = md;
+    }
+    g_lanes = lanes0; g_per_lane = per0;
+    return rc;
 }

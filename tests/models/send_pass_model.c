@@ -40,6 +40,11 @@ typedef struct {
 typedef struct {
     uint64_t pass_a, pass_b, pass_s, pk_a, pk_b, pk_s, b_empty_commit, pass_c, pk_c;
     uint64_t why[8];
+    /* what the case tables of tests/models/send_pass_cases.py ask of a pass (pcc_cases_mirror): regime B split by whether the
+     * token scan decides; the accept chain (g_hold); closed-form passes of a tie of 1/bw on all-even states; passes cut by the top
+     * of t's binade; regime B with and without free mode; the pass position (+ 1) of the first tail drop a scan pass committed;
+     * regime C refused by its own tie alone; the pass position (+ 1) at which the top of the binade first cut a pass */
+    uint64_t pass_bscan, pk_bscan, pass_chain, pk_chain, tie_run, top_cut, pass_free, pass_notfree, first_short, c_tie_refused, top_pos;
 } mstats_t;
 
 static inline uint32_t exp_bits(double x) {
@@ -82,6 +87,14 @@ static int g_lanes = 64;
 #define MAX_PASS (MAX_LANES * PER_LANE)
 static int g_fuzz_straddle = 0;
 void pcc_model_fuzz_straddle(int on) { g_fuzz_straddle = on; }
+/* pcc_cases_mirror only (the entries that were here before it leave both as they are).  g_try_c = 0: regime C is not tried (a team
+ * pass, heavy_mi<.., 4>, has none).  g_hold = 1: the kernel's choice of passes around a pass that a broken precondition ended
+ * after fewer than 32 packets -- the next four passes are not closed forms (chain_left) -- and its accept chain, 64 packets at a
+ * time where the chain's preconditions hold: both send the plain recurrence here, what differs is which pass gets the packets. */
+/* Both are process-wide, like g_lanes: pcc_cases_mirror sets them, runs its cases one after the other on the calling thread and
+ * puts them back; nothing in this file calls model_mi from an OpenMP region, and a caller that ever does must not run next to
+ * pcc_cases_mirror (or must hand the two down as parameters instead). */
+static int g_try_c = 1, g_hold = 0;
 int pcc_model_set_lanes(int lanes) {
     if (lanes < 1 || lanes > MAX_LANES) return -1;
     g_lanes = lanes;
@@ -92,6 +105,7 @@ int pcc_model_set_lanes(int lanes) {
 static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq, double ebw, const uint8_t *loss,
                      rec_t *acc, rec_t *drp, mstats_t *st) {
     uint32_t serial_len = 8;
+    uint32_t chain_left = 0;   /* (g_hold) passes to send without the closed forms */
     while (s->t < end) {
         const double t0 = s->t;
         const double t1s = t0 + gap, G = t1s - t0, t2s = t1s + gap;
@@ -111,7 +125,9 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
         uint32_t e = 0;
         int maxq_above = 0, free_mode = 0;
         if (!ok_t) why = 1;
-        if (ok_t) {
+        else if (chain_left) why = 7;
+        int tie_b = 0;
+        if (ok_t && chain_left == 0) {
             const double x0 = s->q - D0;
             if (G >= ebw && !(x0 > 0.0)) regime = 1;
             else {
@@ -127,6 +143,7 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
                     R = (eb == e) ? ebw : (probe + ebw) - probe;
                     const double err = ebw - R;
                     const int tie = fabs(err) == 0.5 * u;
+                    tie_b = tie;
                     /* everything in units of u must fit an int64 with room for 2^10 packets' worth */
                     const double span = (D0 + (double)PASS * G) * inv_u;
                     ok = ok && span < 4.0e18 && R > 0.0;
@@ -162,8 +179,8 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
          * which differs from the true one by at most j units of v after j accepts -- a position whose decision or
          * landing side is closer than that to its threshold ends the pass (flag) -- then runs the automaton over the
          * accepted packets and adds the accumulated corrections to the queue every packet sees.  */
-        int regime_c = 0;
-        if (ok_t && regime != 1) {
+        int regime_c = 0, c_tried = 0;
+        if (ok_t && regime != 1 && chain_left == 0 && g_try_c) {
             const uint32_t eM = exp_bits(maxq), eq = exp_bits(s->q), eb = exp_bits(ebw);
             const double B = ldexp(1.0, (int)eM - 1023);
             const double x0 = s->q - D0;
@@ -176,12 +193,14 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
                 const double errv = ebw - R0;
                 const double span = (D0 + (double)PASS * G) * inv_v;
                 ok = span < 4.0e18 && R0 > 0.0 && errv != 0.0 && fabs(errv) != 0.5 * v;
+                if (span < 4.0e18 && R0 > 0.0 && fabs(errv) == 0.5 * v && (int64_t)(G * inv_v) < (int64_t)(R0 * inv_v)) st->c_tie_refused++;
                 if (ok) {
                     const int64_t Q0v = (int64_t)(s->q * inv_v), D0v = (int64_t)(D0 * inv_v), Gv = (int64_t)(G * inv_v);
                     const int64_t Rv = (int64_t)(R0 * inv_v), Mv = (int64_t)(maxq * inv_v), Bv = (int64_t)(B * inv_v);
                     const int64_t cl = errv < 0.0 ? 1 : 0, Iv = Rv - cl;
                     if (!(Gv < Rv)) ok = 0;                      /* the sender is not faster than the link: not this regime */
                     if (ok) {
+                        c_tried = 1;
                         const int64_t C = (Mv - Rv) - Q0v + D0v;
                         uint8_t m_k[MAX_PASS], ex_k[MAX_PASS], acc_k[MAX_PASS], flag_k[MAX_PASS], up_k[MAX_PASS];
                         int64_t xi_k[MAX_PASS];
@@ -216,8 +235,10 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
                         int64_t P = Q0v & 1, Cacc = 0;
                         double last_q = 0, last_t = 0;
                         int any = 0;
+                        int cflag = 0;
                         for (uint32_t p = skip; p < (uint32_t)PASS; p++) {
-                            if (!ex_k[p] || flag_k[p]) break;
+                            if (!ex_k[p]) { if (ttop < end) { st->top_cut++; if (!st->top_pos) st->top_pos = p + 1; } break; }
+                            if (flag_k[p]) { cflag = 1; break; }
                             const uint32_t k = p - skip;
                             const double tk = t0 + (double)k * G;
                             const int64_t xt = xi_k[p] + Cacc;                                  /* the true queue this packet sees */
@@ -247,11 +268,13 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
                             serial_len = 8;
                             regime_c = 1;
                         }
+                        if (g_hold && cflag && ncommit < 32) chain_left = 4;
                     }
                 }
             }
         }
         if (regime_c) continue;
+        if (g_hold && c_tried) { regime = 0; why = 5; }   /* (the kernel: regime C was chosen and its first packet flagged -- the serial pass) */
         if (regime == 1) {
             /* ---- A: latency dl, accepted unless lost at random */
             uint32_t n = 0;
@@ -260,7 +283,7 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
             for (uint32_t p = skip; p < PASS; p++) {
                 const uint32_t k = p - skip;
                 const double tk = t0 + (double)k * G;
-                if (!(tk < lim)) break;
+                if (!(tk < lim)) { if (ttop < end) { st->top_cut++; if (!st->top_pos) st->top_pos = p + 1; } break; }
                 const int rnd = loss[s->sent + k];
                 rec_t r;
                 r.lat = dl + 0.0;
@@ -373,8 +396,12 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
             uint32_t ncommit = 0;
             double last_q = 0, last_t = 0;
             int any = 0;
+            int bflag = 0, btop = 0;
+            uint32_t short_at = 0;
             for (uint32_t p = skip; p < PASS; p++) {
-                if (!ex_k[p] || flag_k[p]) break;
+                if (!ex_k[p]) { btop = ttop < end; if (btop && !st->top_pos) st->top_pos = p + 1; break; }
+                if (flag_k[p]) { bflag = 1; break; }
+                if (over && m_k[p] && !acc_k[p] && !short_at) short_at = p + 1;
                 const uint32_t k = p - skip;
                 const double tk = t0 + (double)k * G;
                 const double qc = py_max0(x_k[p]);
@@ -385,11 +412,17 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
                 if (m_k[p]) { last_q = acc_k[p] ? x_k[p] + R : x_k[p]; last_t = tk; any = 1; }
                 ncommit++;
             }
+            if (g_hold && bflag && ncommit < 32) chain_left = 4;
             if (ncommit) {
                 if (any) { s->q = last_q; s->tu = last_t; }
                 s->t = (t0 + (double)(ncommit - 1) * G) + gap;
                 s->sent += ncommit;
                 st->pass_b++; st->pk_b += ncommit;
+                if (over) { st->pass_bscan++; st->pk_bscan += ncommit; }
+                if (tie_b) st->tie_run++;
+                if (btop) st->top_cut++;
+                if (free_mode) st->pass_free++; else st->pass_notfree++;
+                if (short_at && !st->first_short) st->first_short = short_at;
                 serial_len = 8;
                 continue;
             }
@@ -398,6 +431,23 @@ static void model_mi(sstate_t *s, double gap, double end, double dl, double maxq
         }
         /* ---- S: the plain recurrence for a few packets */
         st->why[why]++;
+        if (chain_left) chain_left--;
+        const double tend64 = t0 + 64.0 * G;
+        const int ok_chain = g_hold && (t2s - t1s == G) && (G > 0.0) && (t0 >= 128.0 * gap) && (exp_bits(t0) == exp_bits(tend64)) &&
+                             (s->tu >= maxq) && (s->tu + s->tu >= tend64);
+        if (ok_chain) {   /* the kernel's accept chain: 64 packets, the plain recurrence by other means */
+            uint32_t n = 0;
+            while (n < 64 && s->t < end) {
+                rec_t r;
+                const int dropped = link_send_ref(s->t, loss[s->sent], dl, maxq, ebw, &s->q, &s->tu, &r);
+                if (dropped) drp[s->nd++] = r; else acc[s->na++] = r;
+                s->t += gap;
+                s->sent++;
+                n++;
+            }
+            st->pass_chain++; st->pk_chain += n;
+            continue;
+        }
         uint32_t n = 0;
         while (n < serial_len && s->t < end) {
             rec_t r;
@@ -427,6 +477,49 @@ static double fz_unit(void) { return (double)(fz_next() >> 11) * (1.0 / 90071992
 
 #define MAXPK 70000
 
+/* one fuzzed link and mid-episode state (the generator of pcc_model_fuzz; pcc_model_fuzz_straddle switches the queue limits
+ * just above a power of two on) */
+typedef struct { double bw, dl, queue, lr, maxq, ebw, rate, gap, end; sstate_t s0; } fuzz_case_t;
+static void fuzz_gen(fuzz_case_t *fc) {
+    const double bw = 100.0 + 400.0 * fz_unit();
+    const double dl = 0.05 + 0.45 * fz_unit();
+    double queue = (double)(1 + (long)exp(8.0 * fz_unit()));
+    const int straddle = g_fuzz_straddle && (fz_next() & 1);
+    if (straddle) {   /* a queue limit just above a power of two: the full queue straddles it */
+        const double B = ldexp(1.0, (int)(fz_next() % 7) - 2);       /* 0.25 .. 16 s */
+        queue = ceil(B * bw + fz_unit() * 0.9);
+        if (queue < 2.0) queue = 2.0;
+    }
+    const double lr = (fz_next() & 7) == 0 ? 0.0 : 0.05 * fz_unit();
+    const double maxq = queue / bw, ebw = 1.0 / bw;
+    double rate = (fz_next() & 3) == 0 ? 1000.0 : 40.0 + 960.0 * fz_unit();
+    if (straddle) rate = bw * (1.02 + 0.9 * fz_unit());            /* overdriven: the queue fills and stays full */
+    if (rate > 1000.0) rate = 1000.0;
+    if ((fz_next() & 7) == 0) rate = bw * (0.98 + 0.04 * fz_unit());
+    const double gap = 1.0 / rate;
+    /* a state as an episode would leave it: run the plain recurrence for a random while first */
+    sstate_t s0;
+    memset(&s0, 0, sizeof s0);
+    s0.t = gap;
+    const double warm_rate = straddle ? rate : 40.0 + 960.0 * fz_unit();
+    const double warm_end = straddle ? 4.0 * maxq + 2.0 + fz_unit() * 100.0 : fz_unit() * fz_unit() * 400.0;
+    double q = 0, tu = 0, t = 1.0 / warm_rate;
+    long guard = 0;
+    while (t < warm_end && guard++ < 2000000) {
+        rec_t r;
+        (void)link_send_ref(t, fz_unit() < lr, dl, maxq, ebw, &q, &tu, &r);
+        t += 1.0 / warm_rate;
+    }
+    s0.q = q; s0.tu = tu; s0.t = t;
+    s0.sent = (uint32_t)(fz_next() & 3);   /* Philox block alignment of a take-over */
+    double dur = (0.1 + 30.0 * fz_unit() * fz_unit());
+    if (dur * rate > 60000.0) dur = 60000.0 / rate;
+    const double end = t + dur;
+    fc->bw = bw; fc->dl = dl; fc->queue = queue; fc->lr = lr; fc->maxq = maxq; fc->ebw = ebw; fc->rate = rate; fc->gap = gap;
+    fc->end = end; fc->s0 = s0;
+}
+
+
 /* Fuzz: random links and mid-episode states, the MI sent twice.  Returns the number of mismatches. */
 long pcc_model_fuzz(long n_cases, uint64_t seed, uint64_t *stats_out /* [16] */) {
     fz_state = seed ? seed : 1;
@@ -437,40 +530,11 @@ long pcc_model_fuzz(long n_cases, uint64_t seed, uint64_t *stats_out /* [16] */)
     rec_t *ba = malloc(sizeof(rec_t) * MAXPK), *bd = malloc(sizeof(rec_t) * MAXPK);
     uint8_t *loss = malloc(MAXPK + 8);
     for (long c = 0; c < n_cases; c++) {
-        const double bw = 100.0 + 400.0 * fz_unit();
-        const double dl = 0.05 + 0.45 * fz_unit();
-        double queue = (double)(1 + (long)exp(8.0 * fz_unit()));
-        const int straddle = g_fuzz_straddle && (fz_next() & 1);
-        if (straddle) {   /* a queue limit just above a power of two: the full queue straddles it */
-            const double B = ldexp(1.0, (int)(fz_next() % 7) - 2);       /* 0.25 .. 16 s */
-            queue = ceil(B * bw + fz_unit() * 0.9);
-            if (queue < 2.0) queue = 2.0;
-        }
-        const double lr = (fz_next() & 7) == 0 ? 0.0 : 0.05 * fz_unit();
-        const double maxq = queue / bw, ebw = 1.0 / bw;
-        double rate = (fz_next() & 3) == 0 ? 1000.0 : 40.0 + 960.0 * fz_unit();
-        if (straddle) rate = bw * (1.02 + 0.9 * fz_unit());            /* overdriven: the queue fills and stays full */
-        if (rate > 1000.0) rate = 1000.0;
-        if ((fz_next() & 7) == 0) rate = bw * (0.98 + 0.04 * fz_unit());
-        const double gap = 1.0 / rate;
-        /* a state as an episode would leave it: run the plain recurrence for a random while first */
-        sstate_t s0;
-        memset(&s0, 0, sizeof s0);
-        s0.t = gap;
-        const double warm_rate = straddle ? rate : 40.0 + 960.0 * fz_unit();
-        const double warm_end = straddle ? 4.0 * maxq + 2.0 + fz_unit() * 100.0 : fz_unit() * fz_unit() * 400.0;
-        double q = 0, tu = 0, t = 1.0 / warm_rate;
-        long guard = 0;
-        while (t < warm_end && guard++ < 2000000) {
-            rec_t r;
-            (void)link_send_ref(t, fz_unit() < lr, dl, maxq, ebw, &q, &tu, &r);
-            t += 1.0 / warm_rate;
-        }
-        s0.q = q; s0.tu = tu; s0.t = t;
-        s0.sent = (uint32_t)(fz_next() & 3);   /* Philox block alignment of a take-over */
-        double dur = (0.1 + 30.0 * fz_unit() * fz_unit());
-        if (dur * rate > 60000.0) dur = 60000.0 / rate;
-        const double end = t + dur;
+        fuzz_case_t fc;
+        fuzz_gen(&fc);
+        const double bw = fc.bw, dl = fc.dl, queue = fc.queue, lr = fc.lr, maxq = fc.maxq, ebw = fc.ebw, rate = fc.rate, gap = fc.gap;
+        const double end = fc.end;
+        const sstate_t s0 = fc.s0;
         for (long i = 0; i < MAXPK; i++) loss[i] = fz_unit() < lr;
         sstate_t sa = s0, sb = s0;
         serial_mi(&sa, gap, end, dl, maxq, ebw, loss, aa, ad);
@@ -582,4 +646,107 @@ long pcc_model_episodes(int n_envs, int n_steps, uint64_t seed, uint32_t gid_bas
     (void)total_mis;
     free(aa); free(ad); free(ba); free(bd); free(loss);
     return bad;
+}
+
+/* ======================================================================================================================
+ * Entries for the case tables of tests/models/send_pass_cases.py (the device tests of the passes themselves,
+ * tests/test_send_pass_device.py): cases go in and out as arrays, nothing here asserts.
+ * ====================================================================================================================== */
+typedef struct { double q, tu, t, dl, lr, maxq, ebw, gap, end; uint32_t sent, pad; } mcase_t;   /* 80 bytes */
+
+/* (a) n cases of the generator of pcc_model_fuzz (straddle != 0: of pcc_model_fuzz_straddle(1)), their intervals cut to at most
+ * max_packets packets */
+long pcc_cases_fuzz(long n, uint64_t seed, int straddle, double max_packets, mcase_t *out) {
+    const int straddle0 = g_fuzz_straddle;
+    g_fuzz_straddle = straddle;
+    fz_state = seed ? seed : 1;
+    for (long c = 0; c < n; c++) {
+        fuzz_case_t fc;
+        fuzz_gen(&fc);
+        double end = fc.end;
+        if ((end - fc.s0.t) / fc.gap > max_packets) end = fc.s0.t + max_packets * fc.gap;
+        mcase_t *o = &out[c];
+        o->q = fc.s0.q; o->tu = fc.s0.tu; o->t = fc.s0.t; o->dl = fc.dl; o->lr = fc.lr; o->maxq = fc.maxq; o->ebw = fc.ebw;
+        o->gap = fc.gap; o->end = end; o->sent = fc.s0.sent; o->pad = 0;
+    }
+    g_fuzz_straddle = straddle0;
+    return n;
+}
+
+/* packets of a case's interval, or -1 beyond `room` */
+static long case_packets(const mcase_t *c, long room) {
+    double t = c->t;
+    long k = 0;
+    if (!(c->gap > 0.0) || !(t + c->gap > t)) return -1;
+    while (t < c->end) {
+        if (++k > room) return -1;
+        t += c->gap;
+    }
+    return k;
+}
+
+/* (b) the plain recurrence (serial_mi) on n cases.  Case c owns the elements [off[c], off[c + 1]) of loss (loss[off[c] + k]: the
+ * k-th packet the case sends is lost at random), acc and drp (its accepted / dropped records in send order).  out[c]: the final
+ * state, na / nd counted from 0, sent from the case's.  Returns 0, or -(c + 1) for the first case that does not fit its room. */
+long pcc_cases_plain(long n, const mcase_t *cs, const uint8_t *loss, const int64_t *off, sstate_t *out, rec_t *acc, rec_t *drp) {
+    for (long c = 0; c < n; c++) {
+        if (case_packets(&cs[c], (long)(off[c + 1] - off[c])) < 0) return -(c + 1);
+        sstate_t s;
+        memset(&s, 0, sizeof s);
+        s.q = cs[c].q; s.tu = cs[c].tu; s.t = cs[c].t; s.sent = cs[c].sent;
+        serial_mi(&s, cs[c].gap, cs[c].end, cs[c].dl, cs[c].maxq, cs[c].ebw, loss + off[c] - cs[c].sent, acc + off[c], drp + off[c]);
+        out[c] = s;
+    }
+    return 0;
+}
+
+#define MIRROR_COLS 24
+/* (c) the mirror (model_mi) on the same cases, `lanes` lanes per pass (64: a wavefront; 256: a team, which has no regime C), with
+ * the kernel's choice of passes around short flagged passes (g_hold).  counts[c][MIRROR_COLS]: passes / packets of A (0, 1), B
+ * with the scan (2, 3), B without (4, 5), C (6, 7), the serial pass (8, 9), the accept chain (10, 11); 12 closed-form passes of a
+ * tie of 1/bw; 13 passes a tie refused; 14 passes cut by the top of t's binade; 15 / 16 passes of B with / without free mode;
+ * 17 position + 1 of the first tail drop a scan pass committed; 18 regime C refused by its tie alone; 19 passes refused by
+ * their send times; 20 by the queue's preconditions; 21 nothing committed; 22 held back; 23 pass position + 1 at which the top
+ * of the binade first cut a pass. */
+long pcc_cases_mirror(long n, const mcase_t *cs, const uint8_t *loss, const int64_t *off, int lanes, sstate_t *out, rec_t *acc,
+                      rec_t *drp, uint64_t *counts) {
+    if (lanes != 64 && lanes != 256) return -1;
+    const int lanes0 = g_lanes;
+    g_lanes = lanes; g_try_c = lanes == 64; g_hold = 1;
+    long rc = 0;
+    for (long c = 0; c < n; c++) {
+        if (case_packets(&cs[c], (long)(off[c + 1] - off[c])) < 0) { rc = -(c + 1); break; }
+        sstate_t s;
+        memset(&s, 0, sizeof s);
+        s.q = cs[c].q; s.tu = cs[c].tu; s.t = cs[c].t; s.sent = cs[c].sent;
+        mstats_t st;
+        memset(&st, 0, sizeof st);
+        model_mi(&s, cs[c].gap, cs[c].end, cs[c].dl, cs[c].maxq, cs[c].ebw, loss + off[c] - cs[c].sent, acc + off[c], drp + off[c], &st);
+        out[c] = s;
+        uint64_t *k = counts + c * MIRROR_COLS;
+        k[0] = st.pass_a; k[1] = st.pk_a; k[2] = st.pass_bscan; k[3] = st.pk_bscan; k[4] = st.pass_b - st.pass_bscan;
+        k[5] = st.pk_b - st.pk_bscan; k[6] = st.pass_c; k[7] = st.pk_c; k[8] = st.pass_s; k[9] = st.pk_s; k[10] = st.pass_chain;
+        k[11] = st.pk_chain; k[12] = st.tie_run; k[13] = st.why[4]; k[14] = st.top_cut; k[15] = st.pass_free; k[16] = st.pass_notfree;
+        k[17] = st.first_short; k[18] = st.c_tie_refused; k[19] = st.why[1]; k[20] = st.why[2] + st.why[3] + st.why[6];
+        k[21] = st.why[5]; k[22] = st.why[7]; k[23] = st.top_pos;
+    }
+    g_lanes = lanes0; g_try_c = 1; g_hold = 0;
+    return rc;
+}
+
+/* the loss decisions of n packets from the oracle's Philox, as the device draws them: packet j of the interval is lost iff
+ * `always` or word j & 3 of block j >> 2 (counter: block, mi, episode, gid) is below thr */
+void pcc_cases_philox_loss(long n, uint32_t sent0, uint32_t mi, uint32_t episode, uint32_t gid, uint32_t key0, uint32_t key1, uint32_t thr,
+                           int always, uint8_t *loss) {
+    const uint32_t key[2] = {key0, key1};
+    uint32_t w[4] = {0, 0, 0, 0}, have = 0xFFFFFFFFu;
+    for (long k = 0; k < n; k++) {
+        const uint32_t j = sent0 + (uint32_t)k;
+        if ((j >> 2) != have) {
+            const uint32_t ctr[4] = {j >> 2, mi, episode, gid};
+            philox4x32_10(ctr, key, w);
+            have = j >> 2;
+        }
+        loss[k] = (uint8_t)(always || w[j & 3u] < thr);
+    }
 }

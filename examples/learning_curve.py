@@ -113,6 +113,9 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=None,
                     help="train with PPO(max_grad_norm=...): every curve point carries grad_norm, max_grad_norm_seen, clipped_steps and "
                     "skipped_steps of that iteration's update")
+    ap.add_argument("--rng", default="torch", choices=("torch", "philox"),
+                    help="philox: the rollout's noise, the minibatch orders and the standardised advantages come from the learner's own keyed "
+                    "streams on the device (PPO(rng=\"philox\")): a run does not depend on torch's generators, and the curve of --seed repeats whatever else drew from them")
     ap.add_argument("--episode-ledger", action="store_true",
                     help="train with PPO(track_episodes=True): true_mean_episode_return and episodes in every curve point, and the "
                     "held-out evaluation through pcc_rl_amd.evaluate (the library's episode ledger)")
@@ -121,7 +124,7 @@ def main():
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device=dev, seed=args.seed)
     agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs, track_episodes=args.episode_ledger,
                 normalize_reward=args.normalize_reward, diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows,
-                max_grad_norm=args.max_grad_norm)
+                max_grad_norm=args.max_grad_norm, rng=args.rng)
     untrained = {k: v.clone() for k, v in agent.policy.state_dict().items()}
     iters = max(1, int(round(args.env_steps / (args.envs * args.horizon))))
     curve = []

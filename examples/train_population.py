@@ -67,6 +67,9 @@ def main():
                     help="one limit, or one per member (comma-separated), on the global norm of every optimiser step's gradient; a member's "
                     "step whose gradient is not finite is left out (PopulationPPO(max_grad_norm=...); 0: that guard alone).  The limit is a "
                     "column of the hyper block: a replaced member takes its parent's in a --pbt-every generation")
+    ap.add_argument("--rng", default="torch", choices=("torch", "philox"),
+                    help="philox: the rollout's noise, the minibatch orders and the standardised advantages come from every member's own keyed "
+                    "streams on the device (PopulationPPO(rng=\"philox\")): a run does not depend on torch's generators, and a member repeats when it is run alone with its seed, in a population of another size or in another slot")
     ap.add_argument("--export", default="", help="write every member's policy as TorchScript into <dir>/member<m> (export.export_policy)")
     ap.add_argument("--checkpoint", default="", help="write the whole training state here every --checkpoint-every iterations and at the end")
     ap.add_argument("--checkpoint-every", type=int, default=10)
@@ -94,7 +97,7 @@ def main():
                         seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None, normalize_obs=args.normalize_obs,
                         track_episodes=ledger, normalize_reward=args.normalize_reward,
                         diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows,
-                        max_grad_norm=values(args.max_grad_norm, None) if args.max_grad_norm else None)
+                        max_grad_norm=values(args.max_grad_norm, None) if args.max_grad_norm else None, rng=args.rng)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)

@@ -43,6 +43,9 @@ def main():
     ap.add_argument("--max-grad-norm", type=float, default=None,
                     help="limit the global norm of every optimiser step's gradient to this, and leave out a step whose gradient is not finite, "
                     "on the device (PPO(max_grad_norm=...); 0: that guard alone; stable-baselines3's default is 0.5)")
+    ap.add_argument("--rng", default="torch", choices=("torch", "philox"),
+                    help="philox: the rollout's noise, the minibatch orders and the standardised advantages come from the learner's own keyed "
+                    "streams on the device (PPO(rng=\"philox\")): a run does not depend on torch's generators, and equals the member with the same seed of any population on the same env ids")
     ap.add_argument("--export", default="", help="write the trained policy here as TorchScript (export.export_policy)")
     ap.add_argument("--policy-in-step", action="store_true",
                     help="collect each horizon as one closed-loop call (pcc_rollout): the policy inside the env's launches")
@@ -57,7 +60,8 @@ def main():
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device="cuda:0", seed=0, ring_pools=pools)
     agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
                 policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs, normalize_reward=args.normalize_reward,
-                diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows, max_grad_norm=args.max_grad_norm)
+                diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows, max_grad_norm=args.max_grad_norm,
+                rng=args.rng)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)

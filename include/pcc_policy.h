@@ -357,6 +357,62 @@ int pcc_ppo_minibatch_step_clip_pop(const float *obs, const float *act, const fl
                                     int adam_step, float beta1, float beta2, float eps, float *scratch, float *grad_out, float *stats_out,
                                     float *hyper_grad, double *clip, int64_t clip_stride, void *stream);
 
+/*
+ * Keyed random streams of a learner and the standardisation of its advantages: everything a PPO iteration
+ * draws, as a pure function of (the learner's 64-bit key, iteration, step or epoch, the learner's LOCAL sample index) -- never of
+ * the member's index, of n_envs or n_members other than through n_m = n_envs / n_members, or of any generator's state.  Member m
+ * owns the columns [m * n_m, (m + 1) * n_m) of every [T][n_envs] row, as above; its local env e is column m * n_m + e.  keys: device
+ * uint64 [n_members].  The Philox block of (c0, c1, c2, c3) under a key is Philox4x32-10 (Salmon et al. 2011) with the counter
+ * words c0 .. c3 and the key words {key & 0xffffffff, key >> 32}; its output words are w0 .. w3.  All buffers are caller-owned device
+ * memory; everything is enqueued on `stream`, nothing synchronizes; no atomics.
+ *
+ * pcc_rollout_noise_pop, one launch: noise_out [T][n_envs] float32 standard normals.  The local envs 4 q .. 4 q + 3 of step t share
+ * the block of (q, t, iteration, 0x4E4F4953) under keys[m].  In float64: u1 = ((double)w0 + 1) / 2^32, in (0, 1], so the logarithm is
+ * finite; r = sqrt(-2 log(u1)); env 4 q gets r cos(2 pi w1 / 2^32), env 4 q + 1 gets r sin(2 pi w1 / 2^32); the envs 4 q + 2 and
+ * 4 q + 3 the same from (w2, w3) in place of (w0, w1).  The products are rounded to float32 once.  The device's float64 log, sqrt and
+ * sincospi are good to a few units of the last float64 place, so a value is the correctly rounded one or, rarely, its float32
+ * neighbour; |z| <= sqrt(64 log 2) = 6.67.  words_out: NULL, or uint32 [T][n_envs]: the word w(e & 3) of every env's block, for
+ * tests of this layout.
+ *
+ * pcc_sample_order_pop, one launch: row m of perm_out [n_members][perm_stride] int64 is a permutation of member m's own n = T * n_m
+ * samples, as the global indices t * n_envs + m * n_m + e pcc_ppo_minibatch_step_pop reads; the padding perm_stride - n is never
+ * written.  No sort: position i holds the local sample j = t * n_m + e that a keyed bijection sends i to.  With h the smallest
+ * integer with 4^h >= n and mask = 2^h - 1, F is the balanced Feistel network of 6 rounds on the 2 h bit values x = (L << h) | R:
+ * per round r = 0 .. 5, (L, R) <- (R, L ^ (fmix32(R + k_r) & mask)), the sum in 32 bits, fmix32 the 32-bit finaliser of MurmurHash3
+ * (v ^= v >> 16, v *= 0x85EBCA6B, v ^= v >> 13, v *= 0xC2B2AE35, v ^= v >> 16), k_r = w(r & 3) + r * 0x9E3779B9 in 32 bits from the
+ * block of (epoch, 0, iteration, 0x4F524452) under keys[m].  j is the first of F(i), F(F(i)), ... below n (cycle walking: the walk
+ * follows a cycle of a permutation of [0, 4^h) that starts at i < n, so it ends; 4^h < 4 n, so a walk takes fewer than 4
+ * evaluations on average).  The local permutation depends on (key, iteration, epoch, n) only.
+ *
+ * pcc_adv_standardise_pop, three launches: out [T][n_envs] = float32((a - mean) / (sqrt(var) + 1e-8)) per member over its own n = T *
+ * n_m values a = (double)adv[t][column], float64 throughout: mean = S1 / n, S1 the sum of a; var = S2 / (n - 1), S2 the sum of
+ * (a - mean) * (a - mean) (two passes; n = 1 gives 0 / 0: NaN, as torch's std does); moments_out float64 [n_members][2] = {mean,
+ * var}.  out == adv is allowed.  Both sums are added in this order, which depends on T and n_m alone: lane = local env adds its T
+ * terms in step order from 0.0; the 64 lanes of a wavefront (local envs 64 v .. 64 v + 63; lanes past n_m hold 0.0) by the tree x[j]
+ * += x[j + d] for j < d, d = 32, 16, ..., 1; a workgroup of 256 lanes its four wavefronts' sums in index order; then the G = ceil(n_m /
+ * 256) workgroup sums: sub-lane j of 256 adds those of index [j p, j p + p), p = ceil(G / 256), in index order from 0.0, and the
+ * sub-lanes' sums by the tree x[j] += x[j + s] for j < s, s = 128, 64, ..., 1.  scratch: pcc_adv_standardise_scratch_doubles(T,
+ * n_envs, n_members) doubles (host only; -1 outside the domain).
+ *
+ * A member's noise, order, moments and out are bit-identical to the stand-alone call with its key on a contiguous copy of its
+ * columns (a member is cut into workgroups exactly as a launch over the member alone; no divisibility is asked of the member size).
+ * pcc_rollout_noise / pcc_sample_order / pcc_adv_standardise are the stand-alone forms: the same kernels with one member, the key as
+ * an argument, perm_out [T * n_envs], moments_out [2].
+ * Returns 0; -1, with nothing written and before any device call, outside T >= 1, n_envs >= 1, 1 <= n_members <= 1024, n_envs %
+ * n_members == 0, n_m < 2^31, perm_stride >= T * n_m, or for a NULL noise_out / perm_out / keys / adv / scratch / moments_out / out;
+ * -3 launch failure.
+ */
+int pcc_rollout_noise_pop(float *noise_out, uint32_t *words_out, int T, int64_t n_envs, int n_members, const uint64_t *keys,
+                          uint32_t iteration, void *stream);
+int pcc_sample_order_pop(int64_t *perm_out, int64_t perm_stride, int T, int64_t n_envs, int n_members, const uint64_t *keys,
+                         uint32_t iteration, uint32_t epoch, void *stream);
+int pcc_adv_standardise_scratch_doubles(int T, int64_t n_envs, int n_members);
+int pcc_adv_standardise_pop(const float *adv, int T, int64_t n_envs, int n_members, double *scratch, double *moments_out, float *out,
+                            void *stream);
+int pcc_rollout_noise(float *noise_out, uint32_t *words_out, int T, int64_t n_envs, uint64_t key, uint32_t iteration, void *stream);
+int pcc_sample_order(int64_t *perm_out, int T, int64_t n_envs, uint64_t key, uint32_t iteration, uint32_t epoch, void *stream);
+int pcc_adv_standardise(const float *adv, int T, int64_t n_envs, double *scratch, double *moments_out, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

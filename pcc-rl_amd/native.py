@@ -53,7 +53,9 @@ SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params",
            "pcc_return_scratch_doubles", "pcc_return_stats_update_pop", "pcc_reward_normalise_pop", "pcc_return_stats_update",
            "pcc_reward_normalise",
            "pcc_policy_act_rows_pop", "pcc_update_diag_scratch_doubles", "pcc_update_diag_pop", "pcc_update_diag",
-           "pcc_ppo_minibatch_step_clip_pop"]
+           "pcc_ppo_minibatch_step_clip_pop",
+           "pcc_rollout_noise_pop", "pcc_sample_order_pop", "pcc_adv_standardise_scratch_doubles", "pcc_adv_standardise_pop",
+           "pcc_rollout_noise", "pcc_sample_order", "pcc_adv_standardise"]
 
 
 class PccError(RuntimeError):
@@ -184,6 +186,20 @@ def lib():
     L.pcc_update_diag.argtypes = [vp, vp, vp, vp, vp, i32, i32, i64, vp, i64, f32, vp, vp, vp]
     L.pcc_ppo_minibatch_step_clip_pop.restype = i32   # (pcc_ppo_minibatch_step_pop's arguments, then hyper_grad, clip, clip_stride)
     L.pcc_ppo_minibatch_step_clip_pop.argtypes = L.pcc_ppo_minibatch_step_pop.argtypes[:-1] + [vp, vp, i64, vp]
+    L.pcc_rollout_noise_pop.restype = i32
+    L.pcc_rollout_noise_pop.argtypes = [vp, vp, i32, i64, i32, vp, u32, vp]
+    L.pcc_sample_order_pop.restype = i32
+    L.pcc_sample_order_pop.argtypes = [vp, i64, i32, i64, i32, vp, u32, u32, vp]
+    L.pcc_adv_standardise_scratch_doubles.restype = i32
+    L.pcc_adv_standardise_scratch_doubles.argtypes = [i32, i64, i32]
+    L.pcc_adv_standardise_pop.restype = i32
+    L.pcc_adv_standardise_pop.argtypes = [vp, i32, i64, i32, vp, vp, vp, vp]
+    L.pcc_rollout_noise.restype = i32
+    L.pcc_rollout_noise.argtypes = [vp, vp, i32, i64, u64, u32, vp]
+    L.pcc_sample_order.restype = i32
+    L.pcc_sample_order.argtypes = [vp, i32, i64, u64, u32, u32, vp]
+    L.pcc_adv_standardise.restype = i32
+    L.pcc_adv_standardise.argtypes = [vp, i32, i64, vp, vp, vp, vp]
     L.pcc_debug_pass_stats.restype = i32
     L.pcc_debug_pass_stats.argtypes = [vp, vp, i32]
     L.pcc_debug_path_stats.restype = i32

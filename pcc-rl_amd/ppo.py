@@ -28,6 +28,12 @@ diagnostics=True / target_kl: updiag.UpdateDiagnostics, section 23, and the limi
 gradclip.GradClip, section 24 --, the first observation, the
 checkpoint's common part) and native.call / native.current_stream.  They stay two classes: PPO draws its
 permutations with randperm and takes the last value from the torch module, and a merge would change its numbers.
+
+rng="philox" (both trainers) takes the rollout's noise, every epoch's minibatch order and the standardised
+advantages from streams.LearnerStreams: each learner owns a 64-bit key made from its seed, and what it draws is a pure function of
+(key, iteration, step or epoch, its own local sample index).  There PPO takes the last value from pcc_policy_act too, and PPO(seed=s)
+on a handle of a member's envs, PopulationPPO(members=1, seeds=[s]) on it and the member with seed s of any population compute the
+same bits.  The default, rng="torch", is everything above as it was.
 """
 import math
 
@@ -40,6 +46,7 @@ from .episodes import EpisodeLedger
 from .gradclip import GradClip, limits as _grad_limits
 from .obsnorm import ObsNormalizer
 from .rewnorm import RewardNormalizer
+from .streams import LearnerStreams
 from .updiag import UpdateDiagnostics
 
 
@@ -285,6 +292,36 @@ class _Trainer(object):
             raise ValueError("normalize_obs=True is not supported over a GroupedNetworkEnv: its groups are stepped on their own streams "
                              "and the policy reads the raw observation rows there")
 
+    def _set_rng(self, env, rng, arch=None, fused_update=True):
+        """rng: "torch" -- the rollout's noise and the minibatch permutations from torch's global device generator, the advantages
+        standardised with torch reductions -- or "philox": all three from streams.LearnerStreams, made once the
+        env's device is known (_make_streams).  self.iteration counts the collect() calls under "philox": the counter of the draws.
+        arch=None (PopulationPPO): the caller's own refusals already leave the fused paths alone."""
+        who = type(self).__name__
+        if rng not in ("torch", "philox"):
+            raise ValueError('%s: rng = %r ("torch" or "philox")' % (who, rng))
+        self.rng, self.streams, self.iteration, self._perm_buf = rng, None, 0, None
+        if rng == "torch" or arch is None:
+            return
+        if torch.device(env.device).type != "cuda" or env.n_senders != 1 or len(arch) != 2:
+            raise ValueError('%s(rng="philox") needs the fused rollout (a two-hidden-layer policy, one sender, on the GPU): the framework '
+                             "rollout draws its actions from torch's generator" % who)
+        if not fused_update:
+            raise ValueError('%s(rng="philox") needs the fused update (fused_update=True): the framework update draws its permutations '
+                             "from torch's generator" % who)
+
+    def _make_streams(self, seeds):
+        if self.rng == "philox":
+            self.streams = LearnerStreams(seeds, int(self.env.n_envs), self.env.device)
+
+    def _order(self, T, epoch):
+        """The minibatch order of this iteration's epoch `epoch` under rng="philox": [members][T * n_m] global sample indices, in a
+        buffer that the next call overwrites (the launches that read it are ahead of that one on the stream)."""
+        n = T * self.streams.n_member
+        if self._perm_buf is None or self._perm_buf.shape[1] != n:
+            self._perm_buf = torch.empty((self.streams.members, n), dtype=torch.int64, device=self.env.device)
+        return self.streams.order(T, self.iteration, epoch, out=self._perm_buf)
+
     def _set_reward_norm(self, env, normalize_reward, clip_reward, norm_eps, members=1):
         """normalize_reward: a rewnorm.RewardNormalizer over the env batch, fed by every rollout after it ended (DESIGN.md section
         22): it works with every rollout path."""
@@ -387,6 +424,8 @@ class _Trainer(object):
             sd.update(normalize_reward=True, rew_norm=self.rew_norm.state_dict())
         if self.diagnostics:   # (the options only: the buffers live for one update)
             sd.update(diagnostics=True, target_kl=self.target_kl, diag_row_step=self.diag.row_step)
+        if self.rng == "philox":   # the learners' keys and the counter of their draws (the generator states above are not read)
+            sd.update(rng="philox", streams=self.streams.state_dict(), iteration=int(self.iteration))
         return sd
 
     def _restore(self, sd):
@@ -410,8 +449,15 @@ class _Trainer(object):
         if theirs != mine:
             raise ValueError("the checkpoint was written with (diagnostics, target_kl, row step) = %s, this object has %s: the KL guard "
                              "decides which updates are applied" % (theirs, mine))
+        theirs = sd.get("rng", "torch")
+        if theirs != self.rng:
+            raise ValueError("the checkpoint was written with rng=%r, this object has rng=%r: the two modes draw different rollouts and "
+                             "minibatches" % (theirs, self.rng))
         self.env.restore(sd["env"])
         self._load_params(sd)
+        if self.rng == "philox":
+            self.streams.load_state_dict(sd["streams"])
+            self.iteration = int(sd["iteration"])
         if self.normalize_reward:
             self.rew_norm.load_state_dict(sd["rew_norm"])
         if self.track_episodes:
@@ -429,7 +475,7 @@ class PPO(_Trainer):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
                  epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
                  normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False, normalize_reward=False, clip_reward=10.0,
-                 diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None):
+                 diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None, rng="torch"):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
         optimiser steps per epoch, thousands of launches of a few microseconds of work each.
@@ -455,7 +501,14 @@ class PPO(_Trainer):
         does, and a step whose gradient is not finite changes neither the parameters nor Adam's moments (Adam's step count goes on);
         M = 0 is that guard alone.  One library call per step beside the fused step's kernels (gradclip.GradClip, self.grad_clip;
         DESIGN.md section 24); update() adds grad_norm (the last step's), max_grad_norm_seen, clipped_steps and skipped_steps.  A
-        step that neither clips nor skips leaves the bits the unclipped step leaves.  Needs the fused update."""
+        step that neither clips nor skips leaves the bits the unclipped step leaves.  Needs the fused update.
+        rng="philox": the rollout's noise, every epoch's minibatch order and the standardised advantages come from the learner's own
+        keyed streams on the device (streams.LearnerStreams, self.streams) -- functions of (the key made from
+        `seed`, self.iteration, step or epoch, sample index), none of torch's generators -- and the last value of a rollout from
+        pcc_policy_act: the run equals PopulationPPO(members=1, seeds=[seed], rng="philox") and the member with this seed of any
+        population on the same env ids, bit for bit.  Needs the fused rollout and the fused update; works with every other option.
+        The default "torch" draws from torch's global device generator, as before."""
+        self._set_rng(env, rng, arch, fused_update)
         self._set_grad_clip(env, max_grad_norm, fused_update)
         if self.max_grad_norm is not None:
             self.max_grad_norm = self.max_grad_norm[0]   # (one policy: a number, read at every update like lr: _hyper_now)
@@ -484,6 +537,9 @@ class PPO(_Trainer):
         if fused_update and not self.fused_update:
             _warn_once("PPO.update runs autograd + torch.optim.Adam (no pcc_ppo_minibatch_step for observation length %d, hidden %s, "
                        "%d sender(s) on %s): about 20x slower than the fused step" % (env.obs_dim, list(arch), env.n_senders, env.device))
+        if self.rng == "philox" and not self.fused_update:
+            raise ValueError('PPO(rng="philox") needs the fused update: the library has no pcc_ppo_minibatch_step for observation length '
+                             "%d, hidden %s" % (env.obs_dim, list(arch)))
         if self.fused_update:
             self.flat = self.policy.share_flat()
             self.adam_m, self.adam_v, self.adam_t = torch.zeros_like(self.flat), torch.zeros_like(self.flat), 0
@@ -500,6 +556,7 @@ class PPO(_Trainer):
             self.grad_clip = GradClip(self.param_stride, 1, env.device)
         self.opt = torch.optim.Adam(self.policy.parameters(), lr=lr, eps=self.adam_eps)
         self._first_obs(1, clip_obs, norm_eps)
+        self._make_streams([seed])
         if self.minibatch is None:
             self.minibatch = max(2048, env.n_envs * horizon // 4)
 
@@ -515,15 +572,21 @@ class PPO(_Trainer):
         writes action / log-probability / value into the rollout rows; the env reads that action row and writes the next
         observation, reward and done rows: two library calls and three kernels per step, no framework launch, no copy."""
         env, T, N = self.env, self.horizon, self.env.n_envs
+        philox = self.rng == "philox"
+        if philox:
+            self.iteration += 1
         rows = _RolloutRows(self, T, N)
         fused = self.policy.fused_ok(rows.obs[0]) and env.n_senders == 1
         if self.policy_in_step and not fused:
             raise ValueError("PPO(policy_in_step=True) needs the fused rollout: a two-hidden-layer policy, one sender, on the GPU")
+        if philox and not fused:
+            raise ValueError('PPO(rng="philox") needs the fused rollout: a two-hidden-layer policy, one sender, on the GPU')
         if not fused:
             self._rollout_framework(rows)
         else:
             params = self.policy.flat_params()                     # once per rollout, not per step (a 13-tensor torch.cat)
-            noise = torch.randn((T, N), device=env.device)         # the horizon's draws in one launch
+            # the horizon's draws in one launch: torch's generator, or the learner's keyed stream of this iteration
+            noise = self.streams.noise(T, self.iteration) if philox else torch.randn((T, N), device=env.device)
             if self.policy_in_step:
                 self._rollout_in_step(rows, params, noise)
             elif hasattr(env, "groups"):
@@ -531,8 +594,11 @@ class PPO(_Trainer):
             else:
                 rows.run(env, noise, lambda o, z, a, logp, v: self.policy.act_fused(o, True, params, z, (a, logp, v)))
         obs = rows.finish(self)
-        with torch.no_grad():
-            last_v = self.policy.value(obs)
+        if philox:   # the value output of the kernel the rollout ran, as the population takes it
+            _, _, last_v = self.policy.act_fused(obs, False, params)
+        else:
+            with torch.no_grad():
+                last_v = self.policy.value(obs)
         # never train on corrupted rollouts: an overflowed in-flight ring / an empty ring pool (a trained
         # policy can push many deep-queue envs to MAX_RATE: BatchedNetworkEnv(ring_pools=...)) is flagged, not silent
         env.check_flags()
@@ -606,7 +672,12 @@ class PPO(_Trainer):
         n = obs_b.shape[0] * obs_b.shape[1]
         obs_f, act_f = obs_b.reshape(n, -1), act_b.reshape(n, -1)
         logp_f, adv_f, ret_f = logp_b.reshape(n), adv.reshape(n), ret.reshape(n)
-        adv_f = (adv_f - adv_f.mean()) / (adv_f.std() + 1e-8)
+        if self.rng == "philox":
+            if adv.dim() != 2:
+                raise ValueError('PPO(rng="philox").update needs the rollout\'s [T][N] advantage rows, as collect() returns them')
+            adv_f = self.streams.standardise(adv.contiguous()).reshape(n)
+        else:
+            adv_f = (adv_f - adv_f.mean()) / (adv_f.std() + 1e-8)
         if self.fused_update:
             if self.diagnostics and obs_b.dim() != 3:
                 raise ValueError("PPO(diagnostics=True).update needs the rollout's [T][N][D] observation rows, as collect() returns them")
@@ -686,7 +757,7 @@ class PPO(_Trainer):
         if self.diagnostics:
             self.diag.begin(self.hyper)
         for e in range(self.epochs):
-            perm = torch.randperm(n, device=obs_f.device)
+            perm = self._order(T, e)[0] if self.rng == "philox" else torch.randperm(n, device=obs_f.device)
             for i in range(0, n, self.minibatch):
                 step(obs_f, act_f, logp_f, adv_f, ret_f, perm, i, min(self.minibatch, n - i))
             if self.diagnostics:   # what this epoch did, and whether the next one still updates
@@ -828,12 +899,17 @@ class PopulationPPO(_Trainer):
     max_grad_norm: PPO's option, a scalar or one limit per member: column 5 of hyper, so a replaced member
     takes its parent's through evolve(), which can perturb or bound it by its name; update() adds per-member lists of grad_norm,
     max_grad_norm_seen, clipped_steps and skipped_steps.  A member whose gradient is not finite skips that step alone; the others
-    go on.  None (the default): column 5 stays 0 and the steps are pcc_ppo_minibatch_step_pop's."""
+    go on.  None (the default): column 5 stays 0 and the steps are pcc_ppo_minibatch_step_pop's.
+    rng="philox": PPO's option, per member: member m draws with the key made from seeds[m], so its numbers do
+    not depend on the other members, on their number or on its slot -- it equals PPO(seed=seeds[m], rng="philox") on a handle of its
+    own env ids -- and nothing is drawn from torch's generators."""
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
                  epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False,
-                 normalize_reward=False, clip_reward=10.0, diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None):
+                 normalize_reward=False, clip_reward=10.0, diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None,
+                 rng="torch"):
         members = int(members)
+        self._set_rng(env, rng)
         self._set_normalize(env, normalize_obs)
         if members < 1 or members > 1024:
             raise ValueError("PopulationPPO: members = %d (1 .. 1024)" % members)
@@ -878,6 +954,7 @@ class PopulationPPO(_Trainer):
         if self.max_grad_norm is not None:
             self.grad_clip = GradClip(self.param_stride, members, dev)
         self._first_obs(members, clip_obs, norm_eps)
+        self._make_streams(seeds)
         per_member = self.n_member * horizon
         self.minibatch = min(per_member, max(2048, per_member // 4)) if minibatch is None else int(minibatch)
 
@@ -902,11 +979,14 @@ class PopulationPPO(_Trainer):
         """One rollout of `horizon` steps of the whole batch: per step pcc_policy_act_pop (every member on its slice) and ONE
         env step; then the last values, the env's flags, and pcc_gae_pop with every member's gamma and lambda.  noise: the
         [horizon, n_envs] standard-normal draws (default: drawn here).  Returns PPO.collect()'s tuple; the value and done rows
-        stay in self.val_b / self.done_b."""
+        stay in self.val_b / self.done_b.  With rng="philox" the default is every member's keyed stream of this iteration
+        (self.iteration advances once per call, whether noise is given or not)."""
         env, T, N = self.env, self.horizon, int(self.env.n_envs)
+        if self.rng == "philox":
+            self.iteration += 1
         rows = _RolloutRows(self, T, N)
         if noise is None:
-            noise = torch.randn((T, N), device=env.device)
+            noise = self.streams.noise(T, self.iteration) if self.rng == "philox" else torch.randn((T, N), device=env.device)
         rows.run(env, noise, self._act)
         last_v = torch.empty(N, device=env.device)
         self._act(rows.finish(self), None, None, None, last_v)
@@ -945,11 +1025,13 @@ class PopulationPPO(_Trainer):
 
     def update(self, obs_b, act_b, logp_b, adv, ret, perms=None):
         """`epochs` passes over every member's own samples in minibatches of self.minibatch samples per member.  perms: one
-        [members][T * n_m] tensor per epoch (population_permutations; default: drawn here, one draw per epoch).  With diagnostics
+        [members][T * n_m] tensor per epoch (population_permutations; default: drawn here, one draw per epoch -- with rng="philox" every
+        member's order of (its key, self.iteration, epoch), and the advantages standardised by the library).  With diagnostics
         every epoch ends with the checks of updiag.UpdateDiagnostics on the rollout's rows (the values are self.val_b, collect()'s)."""
         T, N = adv.shape
         n = T * N
-        adv_f = self.normalise(adv).reshape(n)
+        philox = self.rng == "philox"
+        adv_f = (self.streams.standardise(adv.contiguous()) if philox else self.normalise(adv)).reshape(n)
         obs_f, act_f = obs_b.reshape(n, -1).contiguous(), act_b.reshape(n).contiguous()
         logp_f, ret_f = logp_b.reshape(n).contiguous(), ret.reshape(n).contiguous()
         per_member = T * self.n_member
@@ -958,7 +1040,8 @@ class PopulationPPO(_Trainer):
         if self.grad_clip is not None:
             self.grad_clip.begin()
         for e in range(self.epochs):
-            perm = perms[e] if perms is not None else population_permutations(T, N, self.members, device=adv.device)
+            perm = perms[e] if perms is not None else (self._order(T, e) if philox else
+                                                       population_permutations(T, N, self.members, device=adv.device))
             for i in range(0, per_member, self.minibatch):
                 self.minibatch_step(obs_f, act_f, logp_f, adv_f, ret_f, perm, i, min(self.minibatch, per_member - i))
             if self.diagnostics:   # what this epoch did to every member, and who still updates in the next one
@@ -991,7 +1074,8 @@ class PopulationPPO(_Trainer):
         hyper-parameters named in `explore` are multiplied by one of the two `factors` and clamped to `bounds` ({name: (lo, hi)}).
         scores=None (track_episodes only): the ledger's mean finished-episode return since the last such call, read on the device
         (a member without a finished episode scores NaN: last); the ledger's totals are cleared afterwards.
-        The draws are Philox's of (seed, self.generation, member): a run repeats and resumes bit for bit.  Returns (parent, rank)
+        The draws are Philox's of (seed, self.generation, member): a run repeats and resumes bit for bit.  With rng="philox" the
+        learners' keys stay with their slots: a replaced member takes its parent's weights and goes on with its own stream.  Returns (parent, rank)
         as device int32 tensors -- parent[m] == m for a member that was not replaced -- without synchronising.  The host mirror
         hyper_rows is stale from here on (None): hypers() reads the rows back."""
         if not 0.0 <= frac <= 0.5:

@@ -105,6 +105,9 @@ def main():
     ap.add_argument("--normalize-reward", action="store_true",
                     help="train with PPO(normalize_reward=True); the curve's returns and the held-out evaluation stay raw, and every curve "
                     "point carries the value loss")
+    ap.add_argument("--bootstrap-time-limit", action="store_true",
+                    help="train with PPO(bootstrap_time_limit=True): the advantage estimation bootstraps from the value of the observation "
+                    "an episode ended in at the step limit; every curve point carries the value loss")
     ap.add_argument("--diagnostics", action="store_true",
                     help="train with PPO(diagnostics=True): every curve point carries approx_kl, clip_fraction, explained_variance and "
                     "epochs_run of that iteration's update")
@@ -124,7 +127,7 @@ def main():
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device=dev, seed=args.seed)
     agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs, track_episodes=args.episode_ledger,
                 normalize_reward=args.normalize_reward, diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows,
-                max_grad_norm=args.max_grad_norm, rng=args.rng)
+                max_grad_norm=args.max_grad_norm, rng=args.rng, bootstrap_time_limit=args.bootstrap_time_limit)
     untrained = {k: v.clone() for k, v in agent.policy.state_dict().items()}
     iters = max(1, int(round(args.env_steps / (args.envs * args.horizon))))
     curve = []
@@ -176,7 +179,8 @@ def main():
     by = {r["controller"]: r for r in results}
     out = {"what": "PPO (reference hyper-parameters, pi/vf MLP 32-16) on the MI355X simulator, then the trained controller against "
                    "baselines on held-out envs; python examples/learning_curve.py",
-           "normalize_obs": bool(args.normalize_obs), "normalize_reward": bool(args.normalize_reward), "episode_ledger": bool(args.episode_ledger),
+           "normalize_obs": bool(args.normalize_obs), "normalize_reward": bool(args.normalize_reward),
+           "bootstrap_time_limit": bool(args.bootstrap_time_limit), "episode_ledger": bool(args.episode_ledger),
            "diagnostics": bool(agent.diagnostics), "target_kl": args.target_kl, "diag_rows": args.diag_rows, "max_grad_norm": args.max_grad_norm,
            "training": {"envs": args.envs, "horizon": args.horizon, "iterations": iters, "env_steps": iters * args.envs * args.horizon,
                         "reference_budget_env_steps": 6 * 1600 * 410, "wall_s": train_s,

@@ -56,6 +56,10 @@ def main():
                     help="every member divides the rewards its advantage estimation reads by the running standard deviation of its own "
                     "discounted return, with its own gamma (PopulationPPO(normalize_reward=True)); the statistics travel in --checkpoint / "
                     "--resume and with the weights in a --pbt-every generation; scores and what is printed stay raw")
+    ap.add_argument("--bootstrap-time-limit", action="store_true",
+                    help="every done of this env is the step limit, not a terminal state: every member bootstraps its advantage estimation "
+                    "from its own value of the observation the episode ended in, rebuilt on the device "
+                    "(PopulationPPO(bootstrap_time_limit=True)); holds the step records of a rollout, 152 bytes per sample")
     ap.add_argument("--diagnostics", action="store_true",
                     help="after every epoch of an update compute the approximate KL divergence from the rollout's policy, the clip fraction over "
                     "the whole rollout and the explained variance of the value function on the device (PopulationPPO(diagnostics=True))")
@@ -97,7 +101,8 @@ def main():
                         seeds=[int(x) for x in args.seeds.split(",")] if args.seeds else None, normalize_obs=args.normalize_obs,
                         track_episodes=ledger, normalize_reward=args.normalize_reward,
                         diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows,
-                        max_grad_norm=values(args.max_grad_norm, None) if args.max_grad_norm else None, rng=args.rng)
+                        max_grad_norm=values(args.max_grad_norm, None) if args.max_grad_norm else None, rng=args.rng,
+                        bootstrap_time_limit=args.bootstrap_time_limit)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)

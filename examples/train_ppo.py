@@ -33,6 +33,10 @@ def main():
     ap.add_argument("--normalize-reward", action="store_true",
                     help="divide the rewards the advantage estimation reads by the running standard deviation of the discounted return, on the "
                     "device (PPO(normalize_reward=True)); the statistics travel in --checkpoint / --resume; what is printed stays raw")
+    ap.add_argument("--bootstrap-time-limit", action="store_true",
+                    help="every done of this env is the step limit, not a terminal state: bootstrap the advantage estimation from the "
+                    "value of the observation the episode ended in, rebuilt on the device (PPO(bootstrap_time_limit=True)); holds the "
+                    "step records of a rollout, 152 bytes per sample")
     ap.add_argument("--diagnostics", action="store_true",
                     help="after every epoch of an update compute the approximate KL divergence from the rollout's policy, the clip fraction over "
                     "the whole rollout and the explained variance of the value function on the device (PPO(diagnostics=True))")
@@ -61,7 +65,7 @@ def main():
     agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
                 policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs, normalize_reward=args.normalize_reward,
                 diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows, max_grad_norm=args.max_grad_norm,
-                rng=args.rng)
+                rng=args.rng, bootstrap_time_limit=args.bootstrap_time_limit)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)

@@ -413,6 +413,47 @@ int pcc_rollout_noise(float *noise_out, uint32_t *words_out, int T, int64_t n_en
 int pcc_sample_order(int64_t *perm_out, int T, int64_t n_envs, uint64_t key, uint32_t iteration, uint32_t epoch, void *stream);
 int pcc_adv_standardise(const float *adv, int T, int64_t n_envs, double *scratch, double *moments_out, float *out, void *stream);
 
+/*
+ * Time-limit bootstrapping: every done of this env is a truncation at max_steps, so the advantage estimation
+ * may bootstrap from the value of the observation the episode ended in.  With auto-reset that observation is never written -- the
+ * finishing env's row holds the next episode's empty history -- but a rollout's own rows hold all of it.  All buffers are caller-owned
+ * device memory (cols and scales: host memory, read before the call returns); everything is enqueued on `stream`, nothing
+ * synchronizes; no atomics: the same inputs give the same bits.  One sender per env.
+ *
+ * pcc_terminal_obs, one launch.
+ * obs       float32 [T + 1][n_envs][H * F], oldest monitor interval first: the rows the env wrote (row t: before step t); row T is
+ *           not read
+ * steps     float64 [T][n_envs][19]: the step records (include/pcc_sim.h: PCC_STEP_COLS)
+ * done      uint8 [T][n_envs]
+ * cols, scales   [F]: feature f of the newest monitor interval is (float)(steps[t][i][cols[f]] / scales[f]), a float64 division
+ *           rounded to float32 once -- for the env's feature id: column 7 + id and pcc_metric_info's scale
+ * term_obs_out   float32 [n_slots][n_envs][H * F]; term_count_out int32 [n_envs]
+ * The k-th done of env i in order of t (k = 0, 1, ...), at step t, fills term_obs_out[k][i] with obs[t][i][F .. H * F) followed by
+ * the F new features: bit for bit the observation the env would have shown after that step without the reset.  A slot k >= the env's
+ * number of dones is written as zeros; term_count_out[i] = the number of dones of env i, those beyond n_slots included (they are
+ * counted, not stored).  Every element of both outputs is written.
+ * Returns 0; -1, with nothing written and before any device call, for a NULL pointer, T < 1, n_envs < 1, n_slots < 1, H < 1, F
+ * outside 1 .. 16, a column outside 0 .. 18, a scale that is not finite and > 0; -3 launch failure.
+ *
+ * pcc_gae_boot, one launch: pcc_gae -- the same operations in the same order -- but at a done at (t, i) delta = rewards + gamma *
+ * v_term - values and the running sum restarts at delta (the recursion is still cut), v_term = term_value[slot][i], slot = the
+ * number of dones of env i in the rows below t, or 0 for slot >= n_slots (pcc_gae's result).  term_value float32 [n_slots][n_envs]:
+ * the value of term_obs_out[slot][i] (pcc_policy_act_pop with noise == NULL on each slot's rows, value_out alone); term_count int32
+ * [n_envs]: pcc_terminal_obs's counts of the same done rows.  On an env without a done the outputs are bit-identical to pcc_gae's.
+ * pcc_gae_boot_pop: gamma and lambda per member from hyper, as pcc_gae_pop; a member's outputs are bit-identical to pcc_gae_boot on a
+ * contiguous copy of its columns.
+ * Return 0; -1, with nothing written and before any device call, for a NULL pointer, T < 1, n_envs < 1, n_slots < 1, n_members
+ * outside 1 .. 1024, n_envs % n_members != 0; -3 launch failure.
+ */
+int pcc_terminal_obs(const float *obs, const double *steps, const uint8_t *done, int T, int64_t n_envs, int H, int F,
+                     const int32_t *cols, const double *scales, int n_slots, float *term_obs_out, int32_t *term_count_out, void *stream);
+int pcc_gae_boot(const float *rewards, const float *values, const uint8_t *dones, const float *last_value, const float *term_value,
+                 const int32_t *term_count, int n_slots, int T, int64_t n_envs, float gamma, float lam, float *adv_out, float *ret_out,
+                 void *stream);
+int pcc_gae_boot_pop(const float *rewards, const float *values, const uint8_t *dones, const float *last_value, const float *term_value,
+                     const int32_t *term_count, int n_slots, int T, int64_t n_envs, int n_members, const float *hyper, float *adv_out,
+                     float *ret_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

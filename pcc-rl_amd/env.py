@@ -338,17 +338,20 @@ class BatchedNetworkEnv(object):
                                1 if self.auto_reset else 0, self._stream()))
         return self._step_result()
 
-    def step_into(self, actions, obs_out, reward_out, done_out):
+    def step_into(self, actions, obs_out, reward_out, done_out, steps_out=None):
         """step() that writes straight into the caller's tensors -- e.g. rows of a rollout buffer -- instead of the
         env's own output buffers: obs_out float32 [N, S, H*F] (or [N, H*F] with one sender), reward_out float32 [N, S]
-        ([N]), done_out uint8/bool [N], all contiguous on the env's device.  Returns nothing; no copy is made."""
+        ([N]), done_out uint8/bool [N], all contiguous on the env's device.  steps_out: float64 [N, S, 19] for the step's
+        full-precision record (None: the env's own buffer with ``record_steps``, else none).  Returns nothing; no copy is made."""
         a, f64 = self._actions(actions)
         N, S = self.n_envs, self.n_senders
         self._check_out("step_into: an output", obs_out, N * S * self.obs_dim)
         self._check_out("step_into: an output", reward_out, N * S)
         self._check_out("step_into: an output", done_out, N, (torch.uint8, torch.bool))
+        self._check_out("step_into: an output", steps_out, N * S * native.PCC_STEP_COLS, (torch.float64,))
         check(self._L.pcc_step(self._h, _ptr(a), f64, _ptr(obs_out), _ptr(reward_out),
-                               _ptr(done_out), _ptr(self._steps), 1 if self.auto_reset else 0, self._stream()))
+                               _ptr(done_out), _ptr(self._steps if steps_out is None else steps_out), 1 if self.auto_reset else 0,
+                               self._stream()))
         self._t += 1
 
     def step_many(self, actions, obs_out=None, reward_out=None, done_out=None, steps_out=None):

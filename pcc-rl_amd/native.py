@@ -55,7 +55,8 @@ SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params",
            "pcc_policy_act_rows_pop", "pcc_update_diag_scratch_doubles", "pcc_update_diag_pop", "pcc_update_diag",
            "pcc_ppo_minibatch_step_clip_pop",
            "pcc_rollout_noise_pop", "pcc_sample_order_pop", "pcc_adv_standardise_scratch_doubles", "pcc_adv_standardise_pop",
-           "pcc_rollout_noise", "pcc_sample_order", "pcc_adv_standardise"]
+           "pcc_rollout_noise", "pcc_sample_order", "pcc_adv_standardise",
+           "pcc_terminal_obs", "pcc_gae_boot", "pcc_gae_boot_pop"]
 
 
 class PccError(RuntimeError):
@@ -200,6 +201,12 @@ def lib():
     L.pcc_sample_order.argtypes = [vp, i32, i64, u64, u32, u32, vp]
     L.pcc_adv_standardise.restype = i32
     L.pcc_adv_standardise.argtypes = [vp, i32, i64, vp, vp, vp, vp]
+    L.pcc_terminal_obs.restype = i32   # (cols: int32 [F], scales: double [F], host memory)
+    L.pcc_terminal_obs.argtypes = [vp, vp, vp, i32, i64, i32, i32, ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(dbl), i32, vp, vp, vp]
+    L.pcc_gae_boot.restype = i32
+    L.pcc_gae_boot.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, f32, vp, vp, vp]
+    L.pcc_gae_boot_pop.restype = i32
+    L.pcc_gae_boot_pop.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, vp]
     L.pcc_debug_pass_stats.restype = i32
     L.pcc_debug_pass_stats.argtypes = [vp, vp, i32]
     L.pcc_debug_path_stats.restype = i32

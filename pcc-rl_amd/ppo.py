@@ -34,6 +34,11 @@ advantages from streams.LearnerStreams: each learner owns a 64-bit key made from
 (key, iteration, step or epoch, its own local sample index).  There PPO takes the last value from pcc_policy_act too, and PPO(seed=s)
 on a handle of a member's envs, PopulationPPO(members=1, seeds=[s]) on it and the member with seed s of any population compute the
 same bits.  The default, rng="torch", is everything above as it was.
+
+bootstrap_time_limit=True (both trainers): every done of this env is the step limit, so the advantage
+estimation bootstraps from the value of the observation an episode ended in -- rebuilt from the rollout's rows and step records
+(timelimit.TimeLimitBootstrap), valued with the rollout's own parameters, read by pcc_gae_boot / pcc_gae_boot_pop.  The default,
+False, is everything above as it was.
 """
 import math
 
@@ -47,6 +52,7 @@ from .gradclip import GradClip, limits as _grad_limits
 from .obsnorm import ObsNormalizer
 from .rewnorm import RewardNormalizer
 from .streams import LearnerStreams
+from .timelimit import TimeLimitBootstrap
 from .updiag import UpdateDiagnostics
 
 
@@ -178,17 +184,33 @@ class MlpPolicy(nn.Module):
         return a.reshape(n, 1), logp, v
 
 
-def gae(rewards, values, dones, last_value, gamma=0.99, lam=0.95):
+def gae(rewards, values, dones, last_value, gamma=0.99, lam=0.95, term_value=None, term_count=None):
     """Generalised advantage estimation over [T, N] tensors.  dones[t] marks that the env was reset
-    after step t (the next observation belongs to a new episode)."""
+    after step t (the next observation belongs to a new episode).
+    term_value [n_slots, N] with term_count [N] (timelimit.terminal_observations: every env's number of dones in these rows):
+    time-limit bootstrapping, the restatement of pcc_gae_boot -- at a done the next value is term_value[slot] of that env, slot =
+    its dones in the rows before t (0 for a slot >= n_slots), and the running sum restarts at delta; the other rows are what they
+    are without it."""
     T = rewards.shape[0]
     adv = torch.zeros_like(rewards)
     running = torch.zeros_like(last_value)
     next_value = last_value
+    if term_value is not None:
+        if term_count is None:
+            raise ValueError("gae: term_value needs term_count")
+        n_slots = term_value.shape[0]
+        slot = term_count.to(torch.int64).clone()
     for t in range(T - 1, -1, -1):
         alive = 1.0 - dones[t].to(rewards.dtype)
         delta = rewards[t] + gamma * next_value * alive - values[t]
         running = delta + gamma * lam * alive * running
+        if term_value is not None:
+            d = dones[t].to(torch.bool)
+            slot = slot - d.to(torch.int64)
+            stored = d & (slot >= 0) & (slot < n_slots)
+            v_term = term_value.gather(0, slot.clamp(0, n_slots - 1).unsqueeze(0))[0]
+            v_term = torch.where(stored, v_term, torch.zeros_like(v_term))
+            running = torch.where(d, rewards[t] + gamma * v_term - values[t], running)
         adv[t] = running
         next_value = values[t]
     return adv, adv + values
@@ -233,6 +255,8 @@ class _RolloutRows(object):
         self.act = torch.empty((T, N, 1), device=dev)
         self.logp, self.val, self.rew = (torch.empty((T, N), device=dev) for _ in range(3))
         self.done = torch.empty((T, N), dtype=torch.bool, device=dev)
+        # with bootstrap_time_limit every step's float64 record: what the terminal observations are rebuilt from (section 26)
+        self.steps = torch.empty((T, N, 19), dtype=torch.float64, device=dev) if agent.bootstrap_time_limit else None
         self.norm = agent.obs_norm if agent.normalize_obs else None
         if self.norm is None:
             self.dst = self.obs
@@ -252,15 +276,21 @@ class _RolloutRows(object):
         and the env's step from that action row into the next rows: tensors in, tensors out, no framework launch, no copy."""
         for t in range(self.T):
             act(self.obs[t], noise[t], self.act[t].reshape(self.N), self.logp[t], self.val[t])
-            env.step_into(self.act[t], self.dst[t + 1], self.rew[t], self.done[t])
+            env.step_into(self.act[t], self.dst[t + 1], self.rew[t], self.done[t], steps_out=self.step_row(t))
             self.stepped(t)
+
+    def step_row(self, t, lo=None, hi=None):
+        """Row t of the step records (of the envs lo .. hi - 1), or None without bootstrap_time_limit."""
+        return None if self.steps is None else self.steps[t] if lo is None else self.steps[t, lo:hi]
 
     def finish(self, agent):
         """The agent's observation for the next rollout, the normaliser's update from rows 0 .. T - 1 (what the policy saw) and,
         with track_episodes, the reward and done rows into the episode ledger (one library call, whichever way the rows were
         filled); returns the last observation row.  With normalize_reward the raw reward and done rows then update the reward
         normaliser, and the same rows, scaled with the updated statistics (as VecNormalize does: the first rollout is not divided
-        by nothing), are what the advantage estimation reads: self.rew_gae, kept as agent.rew_norm_b.  self.rew stays raw."""
+        by nothing), are what the advantage estimation reads: self.rew_gae, kept as agent.rew_norm_b.  self.rew stays raw.
+        With bootstrap_time_limit the terminal observations are rebuilt here from the raw rows and, with an observation normaliser,
+        normalised BEFORE its update: with the statistics every other row of this rollout was normalised with."""
         T = self.T
         agent.obs = self.obs[T].clone()
         if agent.track_episodes:
@@ -270,6 +300,9 @@ class _RolloutRows(object):
         if agent.normalize_reward:
             agent.rew_norm.update(self.rew, self.done, agent._reward_gamma())
             self.rew_gae = agent.rew_norm_b = agent.rew_norm.normalise(self.rew)
+        if agent.bootstrap_time_limit:
+            agent.time_limit.terminal(self.dst, self.steps, self.done, self.norm)
+            agent.steps_b = self.steps
         if self.norm is not None:
             agent.raw_b, agent.raw_obs = self.dst, self.dst[T].clone()
             self.norm.update(self.dst[:T])
@@ -279,6 +312,8 @@ class _RolloutRows(object):
 class _Trainer(object):
     """What PPO and PopulationPPO do alike outside a rollout: the normalize_obs option, the first observation, and the part of
     a checkpoint that does not depend on how the parameters are kept."""
+
+    bootstrap_time_limit, time_limit, steps_b = False, None, None   # (off until _set_time_limit says otherwise)
 
     def _set_normalize(self, env, normalize_obs, policy_in_step=False):
         """normalize_obs needs the rows between the env and the policy: not with the policy inside the env's launches."""
@@ -334,6 +369,14 @@ class _Trainer(object):
         if env.n_senders != 1:
             raise ValueError("normalize_reward=True needs one sender per env (n_senders = %d): the normaliser's rows are [T][n_envs]" % env.n_senders)
         self.rew_norm = RewardNormalizer(int(env.n_envs), members, clip_reward, norm_eps, device=env.device)
+
+    def _set_time_limit(self, env, bootstrap_time_limit, horizon, members=1):
+        """bootstrap_time_limit: a timelimit.TimeLimitBootstrap over the env batch: every rollout keeps its
+        step records, its terminal observations are rebuilt when it ends, and the advantage estimation bootstraps from their values
+        under the rollout's own parameters.  It works with every rollout path; it holds nothing between two rollouts."""
+        self.bootstrap_time_limit, self.time_limit, self.steps_b = bool(bootstrap_time_limit), None, None
+        if self.bootstrap_time_limit:
+            self.time_limit = TimeLimitBootstrap(env, horizon, members)   # (raises ValueError off the GPU or with two senders)
 
     def _set_diagnostics(self, env, diagnostics, target_kl, diag_rows, horizon, members=1):
         """diagnostics / target_kl: an updiag.UpdateDiagnostics over the env batch, run after every epoch of update() (DESIGN.md
@@ -422,6 +465,8 @@ class _Trainer(object):
             sd.update(track_episodes=True, episodes=self.ledger.state_dict())
         if self.normalize_reward:
             sd.update(normalize_reward=True, rew_norm=self.rew_norm.state_dict())
+        if self.bootstrap_time_limit:   # (the option only: it holds nothing between two rollouts)
+            sd.update(bootstrap_time_limit=True)
         if self.diagnostics:   # (the options only: the buffers live for one update)
             sd.update(diagnostics=True, target_kl=self.target_kl, diag_row_step=self.diag.row_step)
         if self.rng == "philox":   # the learners' keys and the counter of their draws (the generator states above are not read)
@@ -444,6 +489,10 @@ class _Trainer(object):
         if theirs != self.normalize_reward:
             raise ValueError("the checkpoint was written with normalize_reward=%s, this object has normalize_reward=%s: a value "
                              "network without the scale of its targets is meaningless" % (theirs, self.normalize_reward))
+        theirs = bool(sd.get("bootstrap_time_limit", False))
+        if theirs != self.bootstrap_time_limit:
+            raise ValueError("the checkpoint was written with bootstrap_time_limit=%s, this object has bootstrap_time_limit=%s: the "
+                             "value network was trained towards other targets" % (theirs, self.bootstrap_time_limit))
         theirs = (bool(sd.get("diagnostics", False)), sd.get("target_kl"), sd.get("diag_row_step"))
         mine = (self.diagnostics, self.target_kl, self.diag.row_step if self.diagnostics else None)
         if theirs != mine:
@@ -475,7 +524,8 @@ class PPO(_Trainer):
     def __init__(self, env, arch=(32, 16), gamma=0.99, lam=0.95, clip=0.2, ent_coef=0.01, lr=1e-3,
                  epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
                  normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False, normalize_reward=False, clip_reward=10.0,
-                 diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None, rng="torch"):
+                 diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None, rng="torch",
+                 bootstrap_time_limit=False):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
         optimiser steps per epoch, thousands of launches of a few microseconds of work each.
@@ -507,8 +557,16 @@ class PPO(_Trainer):
         `seed`, self.iteration, step or epoch, sample index), none of torch's generators -- and the last value of a rollout from
         pcc_policy_act: the run equals PopulationPPO(members=1, seeds=[seed], rng="philox") and the member with this seed of any
         population on the same env ids, bit for bit.  Needs the fused rollout and the fused update; works with every other option.
-        The default "torch" draws from torch's global device generator, as before."""
+        The default "torch" draws from torch's global device generator, as before.
+        bootstrap_time_limit: every done of this env is a truncation at max_steps, never a terminal state: the advantage estimation
+        bootstraps from the value of the observation the episode ended in instead of from zero (timelimit.TimeLimitBootstrap,
+        self.time_limit).  The env overwrites that observation with the next episode's first one, so it is
+        rebuilt, bit for bit, from the rollout's observation rows and step records (pcc_terminal_obs; the records are 152 bytes per
+        sample, held while the option is on), valued with the rollout's own parameters and read by pcc_gae_boot.  A rollout without
+        a done leaves the bits it leaves without the option.  The rewards collect() returns, the ledger, the reward normaliser and
+        evolve()'s scores are untouched.  One sender per env; works with every rollout path and every other option."""
         self._set_rng(env, rng, arch, fused_update)
+        self._set_time_limit(env, bootstrap_time_limit, horizon)
         self._set_grad_clip(env, max_grad_norm, fused_update)
         if self.max_grad_norm is not None:
             self.max_grad_norm = self.max_grad_norm[0]   # (one policy: a number, read at every update like lr: _hyper_now)
@@ -602,12 +660,38 @@ class PPO(_Trainer):
         # never train on corrupted rollouts: an overflowed in-flight ring / an empty ring pool (a trained
         # policy can push many deep-queue envs to MAX_RATE: BatchedNetworkEnv(ring_pools=...)) is flagged, not silent
         env.check_flags()
-        adv, ret = (gae_fused if fused else gae)(rows.rew_gae, rows.val, rows.done, last_v, self.gamma, self.lam)
+        if self.bootstrap_time_limit:
+            adv, ret = self._gae_time_limit(rows, last_v, params if fused else None)
+        else:
+            adv, ret = (gae_fused if fused else gae)(rows.rew_gae, rows.val, rows.done, last_v, self.gamma, self.lam)
         self.val_b, self.done_b = rows.val, rows.done
         return rows.obs[:T], rows.act, rows.logp, adv, ret, rows.rew
 
     def _reward_gamma(self):
         return self.gamma
+
+    def _gae_time_limit(self, rows, last_v, params):
+        """The advantage estimation under bootstrap_time_limit: the values of the terminal rows (rows.finish made them) with the
+        rollout's parameters -- params: the block the fused rollout ran with, one pcc_policy_act per slot; None: the framework
+        rollout, the torch module -- then pcc_gae_boot, or on the framework path its restatement gae(term_value=...)."""
+        tl = self.time_limit
+        if params is not None:
+            tl.values(lambda o, v: self._value_fused(o, v, params))
+            return tl.gae(rows.rew_gae, rows.val, rows.done, last_v, self.gamma, self.lam)
+        with torch.no_grad():
+            tl.values(lambda o, v: v.copy_(self.policy.value(o)))
+        return gae(rows.rew_gae, rows.val, rows.done, last_v, self.gamma, self.lam, tl.term_val, tl.term_count)
+
+    def _value_fused(self, obs, out, params):
+        """out[N] = the value output of pcc_policy_act on obs [N, D] (no noise, no other output): one launch."""
+        h1, h2 = self.policy.hidden
+        rc = lib().pcc_policy_act(_ptr(obs), obs.shape[0], obs.shape[1], _ptr(params), h1, h2, None, None, None, None, _ptr(out),
+                                  current_stream(obs.device))
+        if rc != 0:   # (as act_fused: a shape outside the library's domain -- the rollout ran on the framework path too)
+            _warn_once("pcc_policy_act has no kernel for %d observations x hidden %d-%d: the terminal values come from the framework "
+                       "path" % (obs.shape[1], h1, h2))
+            with torch.no_grad():
+                out.copy_(self.policy.value(obs))
 
     def _rollout_in_step(self, rows, params, noise):
         """The whole horizon as one pcc_rollout per env (group): the same noise, parameters and rows as the fused loop."""
@@ -615,7 +699,7 @@ class PPO(_Trainer):
         dev = env.device
         outs = (rows.act, rows.logp, rows.val, rows.rew, rows.done.view(torch.uint8))
         if not hasattr(env, "groups"):
-            return env.rollout(params, noise, rows.obs, *outs, arch=arch)
+            return env.rollout(params, noise, rows.obs, *outs, steps_b=rows.steps, arch=arch)
         n = env.group_size
         cur = torch.cuda.current_stream(dev)
         # (a group's rows of [T(+1), N] buffers are strided: each group fills contiguous buffers of its own on its stream)
@@ -628,8 +712,12 @@ class PPO(_Trainer):
                 ob[0] = rows.obs[0, lo:hi]
                 bufs = (torch.empty((T, n, 1), device=dev), torch.empty((T, n), device=dev), torch.empty((T, n), device=dev),
                         torch.empty((T, n), device=dev), torch.empty((T, n), dtype=torch.uint8, device=dev))
-                eg.rollout(params, noise[:, lo:hi].contiguous(), ob, *bufs, arch=arch)
+                if rows.steps is not None:
+                    bufs += (torch.empty((T, n, 19), dtype=torch.float64, device=dev),)
+                eg.rollout(params, noise[:, lo:hi].contiguous(), ob, *bufs, arch=arch)   # (steps_b follows done_b)
                 parts.append((lo, hi, ob, bufs))
+        if rows.steps is not None:
+            outs += (rows.steps,)
         for g, (lo, hi, ob, bufs) in enumerate(parts):
             cur.wait_stream(env.streams[g])
             rows.obs[1:, lo:hi] = ob[1:]
@@ -654,7 +742,8 @@ class PPO(_Trainer):
                 with torch.cuda.stream(env.streams[g]):
                     self.policy.act_fused(rows.obs[t, lo:hi], True, params, noise[t, lo:hi],
                                           (rows.act[t, lo:hi].reshape(n), rows.logp[t, lo:hi], rows.val[t, lo:hi]))
-                    eg.step_into(rows.act[t, lo:hi], rows.obs[t + 1, lo:hi], rows.rew[t, lo:hi], rows.done[t, lo:hi])
+                    eg.step_into(rows.act[t, lo:hi], rows.obs[t + 1, lo:hi], rows.rew[t, lo:hi], rows.done[t, lo:hi],
+                                 steps_out=rows.step_row(t, lo, hi))
         for s in env.streams:
             cur.wait_stream(s)
 
@@ -663,6 +752,10 @@ class PPO(_Trainer):
         for t in range(rows.T):
             a, logp, v = self.policy.act(rows.obs[t])
             rows.act[t], rows.logp[t], rows.val[t] = a, logp, v
+            if rows.steps is not None:   # (the same library call as step(), into the rollout's rows: the step records with them)
+                self.env.step_into(a, rows.dst[t + 1], rows.rew[t], rows.done[t], steps_out=rows.steps[t])
+                rows.stepped(t)
+                continue
             nobs, r, d, _ = self.env.step(a)
             rows.dst[t + 1] = nobs
             rows.stepped(t)
@@ -902,12 +995,15 @@ class PopulationPPO(_Trainer):
     go on.  None (the default): column 5 stays 0 and the steps are pcc_ppo_minibatch_step_pop's.
     rng="philox": PPO's option, per member: member m draws with the key made from seeds[m], so its numbers do
     not depend on the other members, on their number or on its slot -- it equals PPO(seed=seeds[m], rng="philox") on a handle of its
-    own env ids -- and nothing is drawn from torch's generators."""
+    own env ids -- and nothing is drawn from torch's generators.
+    bootstrap_time_limit: PPO's option: the terminal rows are valued by pcc_policy_act_pop, every member its
+    own columns with its own parameters, and pcc_gae_boot_pop reads every member's gamma and lambda.  The option has no state:
+    evolve() and the checkpoint's tensors are what they are without it."""
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
                  epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False,
                  normalize_reward=False, clip_reward=10.0, diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None,
-                 rng="torch"):
+                 rng="torch", bootstrap_time_limit=False):
         members = int(members)
         self._set_rng(env, rng)
         self._set_normalize(env, normalize_obs)
@@ -931,6 +1027,7 @@ class PopulationPPO(_Trainer):
         self._set_episodes(env, track_episodes, members)
         self._set_reward_norm(env, normalize_reward, clip_reward, norm_eps, members)
         self._set_diagnostics(env, diagnostics, target_kl, diag_rows, horizon, members)
+        self._set_time_limit(env, bootstrap_time_limit, horizon, members)
         self.env, self.members, self.arch = env, members, (int(arch[0]), int(arch[1]))
         self.epochs, self.horizon, self.adam_eps = epochs, horizon, 1e-5
         self.n_member = int(env.n_envs) // members
@@ -968,6 +1065,9 @@ class PopulationPPO(_Trainer):
              _ptr(noise), None, _ptr(act), _ptr(logp), _ptr(val), self._stream())
 
     def _gae(self, rew_b, val_b, done_b, last_v):
+        if self.bootstrap_time_limit:   # the terminal rows' values under the parameters as they are now: the rollout's own
+            self.time_limit.values(lambda o, v: self._act(o, None, None, None, v))
+            return self.time_limit.gae_pop(rew_b, val_b, done_b, last_v, self.hyper)
         T, N = rew_b.shape
         adv, ret = torch.empty_like(rew_b), torch.empty_like(rew_b)
         d8 = done_b.view(torch.uint8)

@@ -34,6 +34,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pcc_rl_amd  # noqa: E402
 from pcc_rl_amd.evaluate import evaluate as ledger_evaluate  # noqa: E402
+from pcc_rl_amd.objective import parse as parse_objective  # noqa: E402
 from pcc_rl_amd.ppo import PPO  # noqa: E402
 
 COL_SENT, COL_ACKED, COL_LOST, COL_RATE, COL_TIME, COL_RUN_DUR, COL_REWARD, COL_M0 = 0, 1, 2, 3, 4, 5, 6, 7
@@ -108,6 +109,11 @@ def main():
     ap.add_argument("--bootstrap-time-limit", action="store_true",
                     help="train with PPO(bootstrap_time_limit=True): the advantage estimation bootstraps from the value of the observation "
                     "an episode ended in at the step limit; every curve point carries the value loss")
+    ap.add_argument("--objective", default="",
+                    help="what the controller is trained for, as weights over the step records' metrics: "
+                    "throughput=10,latency=-1000,loss=-2000 is the env's own reward (terms: pcc_rl_amd.objective.TERMS; a term left "
+                    "out weighs 0); the rewards are recomputed on the device from the rollout's step records, 152 bytes per sample "
+                    "(PPO(objective=...)); the curve's returns are then the objective's")
     ap.add_argument("--diagnostics", action="store_true",
                     help="train with PPO(diagnostics=True): every curve point carries approx_kl, clip_fraction, explained_variance and "
                     "epochs_run of that iteration's update")
@@ -127,7 +133,8 @@ def main():
     env = pcc_rl_amd.BatchedNetworkEnv(args.envs, device=dev, seed=args.seed)
     agent = PPO(env, horizon=args.horizon, seed=args.seed, normalize_obs=args.normalize_obs, track_episodes=args.episode_ledger,
                 normalize_reward=args.normalize_reward, diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows,
-                max_grad_norm=args.max_grad_norm, rng=args.rng, bootstrap_time_limit=args.bootstrap_time_limit)
+                max_grad_norm=args.max_grad_norm, rng=args.rng, bootstrap_time_limit=args.bootstrap_time_limit,
+                objective=parse_objective(args.objective) if args.objective else None)
     untrained = {k: v.clone() for k, v in agent.policy.state_dict().items()}
     iters = max(1, int(round(args.env_steps / (args.envs * args.horizon))))
     curve = []
@@ -180,7 +187,7 @@ def main():
     out = {"what": "PPO (reference hyper-parameters, pi/vf MLP 32-16) on the MI355X simulator, then the trained controller against "
                    "baselines on held-out envs; python examples/learning_curve.py",
            "normalize_obs": bool(args.normalize_obs), "normalize_reward": bool(args.normalize_reward),
-           "bootstrap_time_limit": bool(args.bootstrap_time_limit), "episode_ledger": bool(args.episode_ledger),
+           "bootstrap_time_limit": bool(args.bootstrap_time_limit), "objective": args.objective or None, "episode_ledger": bool(args.episode_ledger),
            "diagnostics": bool(agent.diagnostics), "target_kl": args.target_kl, "diag_rows": args.diag_rows, "max_grad_norm": args.max_grad_norm,
            "training": {"envs": args.envs, "horizon": args.horizon, "iterations": iters, "env_steps": iters * args.envs * args.horizon,
                         "reference_budget_env_steps": 6 * 1600 * 410, "wall_s": train_s,

@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import pcc_rl_amd  # noqa: E402
+from pcc_rl_amd.objective import parse as parse_objective  # noqa: E402
 from pcc_rl_amd.ppo import PPO  # noqa: E402
 
 
@@ -37,6 +38,11 @@ def main():
                     help="every done of this env is the step limit, not a terminal state: bootstrap the advantage estimation from the "
                     "value of the observation the episode ended in, rebuilt on the device (PPO(bootstrap_time_limit=True)); holds the "
                     "step records of a rollout, 152 bytes per sample")
+    ap.add_argument("--objective", default="",
+                    help="what the controller is trained for, as weights over the step records' metrics: "
+                    "throughput=10,latency=-1000,loss=-2000 is the env's own reward (terms: pcc_rl_amd.objective.TERMS; a term left "
+                    "out weighs 0); the rewards are recomputed on the device from the rollout's step records, 152 bytes per sample "
+                    "(PPO(objective=...))")
     ap.add_argument("--diagnostics", action="store_true",
                     help="after every epoch of an update compute the approximate KL divergence from the rollout's policy, the clip fraction over "
                     "the whole rollout and the explained variance of the value function on the device (PPO(diagnostics=True))")
@@ -65,7 +71,8 @@ def main():
     agent = PPO(env, arch=tuple(int(x) for x in args.arch.split(",")), gamma=args.gamma, horizon=args.horizon,
                 policy_in_step=args.policy_in_step, normalize_obs=args.normalize_obs, normalize_reward=args.normalize_reward,
                 diagnostics=args.diagnostics, target_kl=args.target_kl, diag_rows=args.diag_rows, max_grad_norm=args.max_grad_norm,
-                rng=args.rng, bootstrap_time_limit=args.bootstrap_time_limit)
+                rng=args.rng, bootstrap_time_limit=args.bootstrap_time_limit,
+                objective=parse_objective(args.objective) if args.objective else None)
     first = 0
     if args.resume:
         ck = torch.load(args.resume)

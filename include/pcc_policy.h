@@ -454,6 +454,51 @@ int pcc_gae_boot_pop(const float *rewards, const float *values, const uint8_t *d
                      const int32_t *term_count, int n_slots, int T, int64_t n_envs, int n_members, const float *hyper, float *adv_out,
                      float *ret_out, void *stream);
 
+/*
+ * Reward objectives: the reward rows of a rollout recomputed from its step records under per-member weights
+ * over six of their metrics.  The env's own reward is the fixed combination (10 recv_rate / 12000 - 1e3 avg_latency - 2e3 loss_ratio)
+ * 1e-3; every metric it is made of is in the float64 step record, so another combination needs no env kernel.  All buffers are
+ * caller-owned device memory; everything is enqueued on `stream`, nothing synchronizes; no atomics: the same inputs give the same
+ * bits.  One sender per env.
+ * steps       float64 [T][n_envs][PCC_STEP_COLS] (include/pcc_sim.h): m[X] below is column PCC_COL_METRIC0 + PCC_M_X of a record
+ * weights     float64 [n_members][PCC_OBJ_TERMS]: member m owns the columns [m * n_m, (m + 1) * n_m) of every row, n_m = n_envs /
+ *             n_members, and its row of weights holds for them; the caller keeps them finite
+ * reward_out  float32 [T][n_envs]
+ * sums        float64 [n_members][PCC_OBJ_TERMS + 1], or NULL (then the second launch is left out)
+ * scratch     pcc_objective_scratch_doubles(T, n_envs, n_members) doubles (host only; -1 outside the domain)
+ * The reward of a sample, in float64: the terms of the enum below in index order, a term whose weight is exactly 0 left out -- its
+ * metric is never read, so an unused column cannot make the reward NaN; the first term that is not left out starts the sum, every
+ * later one is added to it; the sum times 1e-3 (the env's kRewardScale), rounded to float32 once.  No term at all gives 0.0f.  One
+ * multiply, one divide and one add per operation written, no contraction: with the weights (10, -1e3, -2e3, 0, 0, 0) reward_out holds
+ * the bits of the env's own reward rows, and of (float)steps[..][PCC_COL_REWARD].
+ * sums[m][k], k < PCC_OBJ_TERMS, is the sum over the member's T * n_m samples of weighted term k before the scale (0 for a term left
+ * out), sums[m][PCC_OBJ_TERMS] that of the float32 rewards widened to float64.  Every sum is added in this order, which depends on T
+ * and n_m alone: lane = local env adds its T values in step order from +0.0; the 64 lanes of a wavefront (local envs 64 v .. 64 v +
+ * 63; lanes past n_m hold 0.0) by the tree x[j] += x[j + d] for j < d, d = 32, 16, ..., 1; a workgroup of 256 lanes its four
+ * wavefronts' sums in index order; then the G = ceil(n_m / 256) workgroup sums: sub-lane j of 256 adds those of index [j p, j p + p),
+ * p = ceil(G / 256), in index order from 0.0, and the sub-lanes' sums by the tree x[j] += x[j + s] for j < s, s = 128, 64, ..., 1.
+ * A member's rewards and sums are bit-identical to the stand-alone call with its weights on a contiguous copy of its columns (a
+ * member is cut into workgroups exactly as a launch over the member alone; no divisibility is asked of the member size).
+ * pcc_reward_objective is the stand-alone form: the same kernels with one member, weights [PCC_OBJ_TERMS], sums [PCC_OBJ_TERMS + 1].
+ * Returns 0; -1, with nothing written and before any device call, for a NULL steps / weights / reward_out / scratch, T < 1, n_envs <
+ * 1, n_members outside 1 .. 1024, n_envs % n_members != 0, or T * n_envs records beyond what a 64-bit byte offset holds; -3 launch
+ * failure.
+ */
+enum {
+    PCC_OBJ_THROUGHPUT = 0,     /* (w * m[RECV_RATE]) / 12000.0   packets/s */
+    PCC_OBJ_LATENCY,            /*  w * m[AVG_LATENCY]            seconds   */
+    PCC_OBJ_LOSS,               /*  w * m[LOSS_RATIO]                       */
+    PCC_OBJ_LATENCY_INFLATION,  /*  w * m[SENT_LATENCY_INFLATION]           */
+    PCC_OBJ_LATENCY_RATIO,      /*  w * m[LATENCY_RATIO]                    */
+    PCC_OBJ_SEND_RATE,          /* (w * m[SEND_RATE]) / 12000.0             */
+    PCC_OBJ_TERMS
+};
+int pcc_objective_scratch_doubles(int T, int64_t n_envs, int n_members);
+int pcc_reward_objective_pop(const double *steps, int T, int64_t n_envs, int n_members, const double *weights, float *reward_out,
+                             double *sums, double *scratch, void *stream);
+int pcc_reward_objective(const double *steps, int T, int64_t n_envs, const double *weights, float *reward_out, double *sums,
+                         double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

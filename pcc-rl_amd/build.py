@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 # one translation unit per kernel family (each kernel is register-allocated on its own) + the C ABI + the PPO caller's kernels
 UNITS = ["pcc_sim.hip", "pcc_send.hip", "pcc_send_restart.hip", "pcc_retire.hip", "pcc_small.hip", "pcc_fused.hip", "pcc_noise_sorted.hip", "pcc_snapshot.hip",
          "pcc_policy.hip", "pcc_ppo.hip", "pcc_mlp_tiles_d32.hip", "pcc_mlp_tiles_d64.hip", "pcc_mlp_tiles_d128.hip", "pcc_pbt.hip", "pcc_obsnorm.hip", "pcc_episodes.hip",
-         "pcc_rewnorm.hip", "pcc_updiag.hip", "pcc_gradclip.hip", "pcc_streams.hip", "pcc_timelimit.hip"]
+         "pcc_rewnorm.hip", "pcc_updiag.hip", "pcc_gradclip.hip", "pcc_streams.hip", "pcc_timelimit.hip", "pcc_objective.hip"]
 SRCS = [os.path.join(CSRC, u) for u in UNITS]
 HEADERS = [os.path.join(CSRC, h) for h in ("pcc_dev.h", "pcc_kernels.h", "pcc_wave_pass.h", "pcc_send_item.h", "pcc_send_bodies.h", "pcc_retire_env.h", "pcc_policy_dev.h", "pcc_mlp_tiles.h", "pcc_snapshot.h")]
 INCLUDE = os.path.join(ROOT, "include")

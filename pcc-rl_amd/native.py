@@ -56,7 +56,8 @@ SYMBOLS = ["pcc_last_error", "pcc_create", "pcc_destroy", "pcc_set_link_params",
            "pcc_ppo_minibatch_step_clip_pop",
            "pcc_rollout_noise_pop", "pcc_sample_order_pop", "pcc_adv_standardise_scratch_doubles", "pcc_adv_standardise_pop",
            "pcc_rollout_noise", "pcc_sample_order", "pcc_adv_standardise",
-           "pcc_terminal_obs", "pcc_gae_boot", "pcc_gae_boot_pop"]
+           "pcc_terminal_obs", "pcc_gae_boot", "pcc_gae_boot_pop",
+           "pcc_objective_scratch_doubles", "pcc_reward_objective_pop", "pcc_reward_objective"]
 
 
 class PccError(RuntimeError):
@@ -207,6 +208,12 @@ def lib():
     L.pcc_gae_boot.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i64, f32, f32, vp, vp, vp]
     L.pcc_gae_boot_pop.restype = i32
     L.pcc_gae_boot_pop.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i64, i32, vp, vp, vp, vp]
+    L.pcc_objective_scratch_doubles.restype = i32
+    L.pcc_objective_scratch_doubles.argtypes = [i32, i64, i32]
+    L.pcc_reward_objective_pop.restype = i32   # (steps, T, n_envs, n_members, weights, reward_out, sums, scratch, stream)
+    L.pcc_reward_objective_pop.argtypes = [vp, i32, i64, i32, vp, vp, vp, vp, vp]
+    L.pcc_reward_objective.restype = i32
+    L.pcc_reward_objective.argtypes = [vp, i32, i64, vp, vp, vp, vp, vp]
     L.pcc_debug_pass_stats.restype = i32
     L.pcc_debug_pass_stats.argtypes = [vp, vp, i32]
     L.pcc_debug_path_stats.restype = i32

@@ -39,6 +39,11 @@ bootstrap_time_limit=True (both trainers): every done of t
 estimation bootstraps from the value of the observation an episode ended in -- rebuilt from the rollout's rows and step records
 (timelimit.TimeLimitBootstrap), valued with the rollout's own parameters, read by pcc_gae_boot / pcc_gae_boot_pop.  The default,
 False, is everything above as it was.
+
+objective=... (both trainers): what the learner is trained for.  Every rollout keeps its step records, and when
+it ends its reward rows are recomputed from them under the learner's weights (objective.RewardObjective, one library call for all
+members): the ledger, the reward normaliser, the advantage estimation and what collect() returns see those rows; the env's own stay
+in self.env_rew_b.  The default, None, is everything above as it was.
 """
 import math
 
@@ -49,6 +54,7 @@ from .env import BatchedNetworkEnv, _ptr
 from .native import call, current_stream, lib
 from .episodes import EpisodeLedger
 from .gradclip import GradClip, limits as _grad_limits
+from .objective import RewardObjective
 from .obsnorm import ObsNormalizer
 from .rewnorm import RewardNormalizer
 from .streams import LearnerStreams
@@ -255,8 +261,10 @@ class _RolloutRows(object):
         self.act = torch.empty((T, N, 1), device=dev)
         self.logp, self.val, self.rew = (torch.empty((T, N), device=dev) for _ in range(3))
         self.done = torch.empty((T, N), dtype=torch.bool, device=dev)
-        # with bootstrap_time_limit every step's float64 record: what the terminal observations are rebuilt from (section 26)
-        self.steps = torch.empty((T, N, 19), dtype=torch.float64, device=dev) if agent.bootstrap_time_limit else None
+        # with bootstrap_time_limit every step's float64 record: what the terminal observations are rebuilt from (section 26); with
+        # an objective: what the learner's reward rows are computed from (section 27).  One buffer for both.
+        keep = agent.bootstrap_time_limit or agent.objective is not None
+        self.steps = torch.empty((T, N, 19), dtype=torch.float64, device=dev) if keep else None
         self.norm = agent.obs_norm if agent.normalize_obs else None
         if self.norm is None:
             self.dst = self.obs
@@ -280,7 +288,7 @@ class _RolloutRows(object):
             self.stepped(t)
 
     def step_row(self, t, lo=None, hi=None):
-        """Row t of the step records (of the envs lo .. hi - 1), or None without bootstrap_time_limit."""
+        """Row t of the step records (of the envs lo .. hi - 1), or None when the rollout keeps none."""
         return None if self.steps is None else self.steps[t] if lo is None else self.steps[t, lo:hi]
 
     def finish(self, agent):
@@ -290,12 +298,18 @@ class _RolloutRows(object):
         normaliser, and the same rows, scaled with the updated statistics (as VecNormalize does: the first rollout is not divided
         by nothing), are what the advantage estimation reads: self.rew_gae, kept as agent.rew_norm_b.  self.rew stays raw.
         With bootstrap_time_limit the terminal observations are rebuilt here from the raw rows and, with an observation normaliser,
-        normalised BEFORE its update: with the statistics every other row of this rollout was normalised with."""
+        normalised BEFORE its update: with the statistics every other row of this rollout was normalised with.
+        With an objective, FIRST of all, the rows the env wrote become agent.env_rew_b and self.rew the objective's rows of the step
+        records: everything below, and whoever reads self.rew after this call, sees the learner's reward.  The ledger then has the
+        step-record channel "reward" beside channel 0: the env's own returns."""
         T = self.T
         agent.obs = self.obs[T].clone()
+        if agent.objective is not None:
+            agent.env_rew_b, agent.steps_b = self.rew, self.steps
+            self.rew = agent.objective.apply(self.steps)
         if agent.track_episodes:
             agent._episodes_before = agent.ledger.totals()[:, :3].clone()
-            agent.ledger.update(self.rew, self.done)
+            agent.ledger.update(self.rew, self.done, self.steps)   # (the records are read by a ledger with step-record channels only)
         self.rew_gae = self.rew
         if agent.normalize_reward:
             agent.rew_norm.update(self.rew, self.done, agent._reward_gamma())
@@ -314,6 +328,7 @@ class _Trainer(object):
     a checkpoint that does not depend on how the parameters are kept."""
 
     bootstrap_time_limit, time_limit, steps_b = False, None, None   # (off until _set_time_limit says otherwise)
+    objective, env_rew_b = None, None                                # (off until _set_objective says otherwise)
 
     def _set_normalize(self, env, normalize_obs, policy_in_step=False):
         """normalize_obs needs the rows between the env and the policy: not with the policy inside the env's launches."""
@@ -378,6 +393,26 @@ class _Trainer(object):
         if self.bootstrap_time_limit:
             self.time_limit = TimeLimitBootstrap(env, horizon, members)   # (raises ValueError off the GPU or with two senders)
 
+    def _set_objective(self, env, objective, members=1):
+        """objective: an objective.RewardObjective over the env batch, or what makes one: a dict of term
+        weights, a sequence of them, or one of either per member.  Every rollout keeps its step records and its reward rows are the
+        objective's; it works with every rollout path.  Call it before _set_episodes: the ledger then carries the env's own reward
+        as a step-record channel."""
+        self.objective, self.env_rew_b = None, None
+        if objective is None:
+            return
+        if torch.device(env.device).type != "cuda":
+            raise ValueError("objective=... runs HIP kernels: it needs the env on the GPU (device=%r); there is no CPU path" % (env.device,))
+        if env.n_senders != 1:
+            raise ValueError("objective=... needs one sender per env (n_senders = %d): the rows are [T][n_envs]" % env.n_senders)
+        if isinstance(objective, RewardObjective):
+            if (objective.n_envs, objective.members) != (int(env.n_envs), members):
+                raise ValueError("objective: a RewardObjective of (n_envs, members) = (%d, %d) for a trainer of (%d, %d)"
+                                 % (objective.n_envs, objective.members, env.n_envs, members))
+            self.objective = objective
+        else:
+            self.objective = RewardObjective(int(env.n_envs), members, objective, device=env.device)
+
     def _set_diagnostics(self, env, diagnostics, target_kl, diag_rows, horizon, members=1):
         """diagnostics / target_kl: an updiag.UpdateDiagnostics over the env batch, run after every epoch of update() (DESIGN.md
         section 23).  target_kl implies diagnostics; diag_rows=R reads about R of the horizon's rows (every max(1, T // R)-th)."""
@@ -423,7 +458,8 @@ class _Trainer(object):
             return
         if env.n_senders != 1:
             raise ValueError("track_episodes=True needs one sender per env (n_senders = %d): the ledger's rows are [T][n_envs]" % env.n_senders)
-        self.ledger = EpisodeLedger(int(env.n_envs), members, device=env.device)
+        # under an objective channel 0 is the learner's reward; the env's own stays beside it as the step-record channel "reward"
+        self.ledger = EpisodeLedger(int(env.n_envs), members, ("reward",) if self.objective is not None else (), device=env.device)
 
     def _episode_stats(self):
         """The episodes finished in the last rollout, as the difference of the ledger's totals after and before it: per member
@@ -467,6 +503,8 @@ class _Trainer(object):
             sd.update(normalize_reward=True, rew_norm=self.rew_norm.state_dict())
         if self.bootstrap_time_limit:   # (the option only: it holds nothing between two rollouts)
             sd.update(bootstrap_time_limit=True)
+        if self.objective is not None:   # the weights: what the value network's targets are made of
+            sd.update(objective=True, objective_state=self.objective.state_dict())
         if self.diagnostics:   # (the options only: the buffers live for one update)
             sd.update(diagnostics=True, target_kl=self.target_kl, diag_row_step=self.diag.row_step)
         if self.rng == "philox":   # the learners' keys and the counter of their draws (the generator states above are not read)
@@ -493,6 +531,10 @@ class _Trainer(object):
         if theirs != self.bootstrap_time_limit:
             raise ValueError("the checkpoint was written with bootstrap_time_limit=%s, this object has bootstrap_time_limit=%s: the "
                              "value network was trained towards other targets" % (theirs, self.bootstrap_time_limit))
+        theirs = bool(sd.get("objective", False))
+        if theirs != (self.objective is not None):
+            raise ValueError("the checkpoint was written with objective=%s, this object has objective=%s: the value network was "
+                             "trained towards another reward" % ("..." if theirs else None, "..." if self.objective is not None else None))
         theirs = (bool(sd.get("diagnostics", False)), sd.get("target_kl"), sd.get("diag_row_step"))
         mine = (self.diagnostics, self.target_kl, self.diag.row_step if self.diagnostics else None)
         if theirs != mine:
@@ -509,6 +551,8 @@ class _Trainer(object):
             self.iteration = int(sd["iteration"])
         if self.normalize_reward:
             self.rew_norm.load_state_dict(sd["rew_norm"])
+        if self.objective is not None:
+            self.objective.load_state_dict(sd["objective_state"])
         if self.track_episodes:
             self.ledger.load_state_dict(sd["episodes"])
         self.obs = sd["obs"].to(dev).clone()
@@ -525,7 +569,7 @@ class PPO(_Trainer):
                  epochs=4, minibatch=None, horizon=64, seed=0, fused_update=True, policy_in_step=False,
                  normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False, normalize_reward=False, clip_reward=10.0,
                  diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None, rng="torch",
-                 bootstrap_time_limit=False):
+                 bootstrap_time_limit=False, objective=None):
         """minibatch None = a quarter of the rollout, at least 2048: the reference's ratio (optim_batchsize 2048 of a
         timesteps_per_actorbatch of 8192, stable_solve.py:52) -- at 65 536 envs x 64 steps a fixed 2048 would be 2 048
         optimiser steps per epoch, thousands of launches of a few microseconds of work each.
@@ -564,9 +608,18 @@ class PPO(_Trainer):
         rebuilt, bit for bit, from the rollout's observation rows and step records (pcc_terminal_obs; the records are 152 bytes per
         sample, held while the option is on), valued with the rollout's own parameters and read by pcc_gae_boot.  A rollout without
         a done leaves the bits it leaves without the option.  The rewards collect() returns, the ledger, the reward normaliser and
-        evolve()'s scores are untouched.  One sender per env; works with every rollout path and every other option."""
+        evolve()'s scores are untouched.  One sender per env; works with every rollout path and every other option.
+        objective: what the controller is trained for, as weights over the step records' metrics (objective.RewardObjective,
+        self.objective): a dict such as {"throughput": 10, "latency": -1e3, "loss": -2e3} -- that one is
+        RewardObjective.DEFAULT, the env's own reward, which reproduces it bit for bit --, six numbers in the order of
+        objective.TERMS, or a RewardObjective.  The rollout keeps its step records (152 bytes per sample, the buffer
+        bootstrap_time_limit holds) and its reward rows are recomputed from them when it ends: the episode ledger's channel 0, the
+        reward normaliser, the advantage estimation, collect()'s sixth value and mean_step_reward are the objective's; the env's own
+        rows stay in self.env_rew_b, its returns in the ledger's channel "reward" and in the env's last_return.  iterate() adds
+        objective_terms: {term: mean weighted term}.  One sender per env; works with every rollout path and every other option."""
         self._set_rng(env, rng, arch, fused_update)
         self._set_time_limit(env, bootstrap_time_limit, horizon)
+        self._set_objective(env, objective)
         self._set_grad_clip(env, max_grad_norm, fused_update)
         if self.max_grad_norm is not None:
             self.max_grad_norm = self.max_grad_norm[0]   # (one policy: a number, read at every update like lr: _hyper_now)
@@ -901,6 +954,8 @@ class PPO(_Trainer):
         obs_b, act_b, logp_b, adv, ret, rew = self.collect()
         stats = self.update(obs_b, act_b, logp_b, adv, ret)
         stats["mean_step_reward"] = float(rew.mean())
+        if self.objective is not None:
+            stats["objective_terms"] = self.objective.report()["terms"][0]
         if self.track_episodes:
             eps, ret, length = self._episode_stats()
             stats.update(episodes=eps[0], mean_episode_return=ret[0], mean_episode_length=length[0])
@@ -998,18 +1053,25 @@ class PopulationPPO(_Trainer):
     own env ids -- and nothing is drawn from torch's generators.
     bootstrap_time_limit: PPO's option: the terminal rows are valued by pcc_policy_act_pop, every member its
     own columns with its own parameters, and pcc_gae_boot_pop reads every member's gamma and lambda.  The option has no state:
-    evolve() and the checkpoint's tensors are what they are without it."""
+    evolve() and the checkpoint's tensors are what they are without it.
+    objective: PPO's option: one objective for all members, or a list of one per member -- a sweep over what
+    the controllers are trained for.  The weights stay with their slots through evolve(), as the keyed streams do: a replaced member
+    goes on with its parent's parameters under its own objective.  evolve(scores=None) ranks the ledger's returns, which under
+    different objectives do not compare: it raises then; explicit scores work (for instance the ledger's channel "reward").
+    iterate() adds objective_terms, a list of {term: mean weighted term}."""
 
     def __init__(self, env, members, arch=(32, 16), lr=1e-3, clip=0.2, ent_coef=0.01, gamma=0.99, lam=0.95, seeds=None,
                  epochs=4, minibatch=None, horizon=64, normalize_obs=False, clip_obs=10.0, norm_eps=1e-8, track_episodes=False,
                  normalize_reward=False, clip_reward=10.0, diagnostics=False, target_kl=None, diag_rows=None, max_grad_norm=None,
-                 rng="torch", bootstrap_time_limit=False):
+                 rng="torch", bootstrap_time_limit=False, objective=None):
         members = int(members)
         self._set_rng(env, rng)
         self._set_normalize(env, normalize_obs)
         if members < 1 or members > 1024:
             raise ValueError("PopulationPPO: members = %d (1 .. 1024)" % members)
         self._set_grad_clip(env, max_grad_norm, True, members)
+        if int(env.n_envs) % members == 0:   # (else refused below, in the words of before)
+            self._set_objective(env, objective, members)
         if len(arch) != 2:
             raise ValueError("PopulationPPO needs a policy of two hidden layers (arch = %r)" % (tuple(arch),))
         if int(env.n_envs) % members != 0:
@@ -1163,6 +1225,8 @@ class PopulationPPO(_Trainer):
         obs_b, act_b, logp_b, adv, ret, rew = self.collect()
         stats = self.update(obs_b, act_b, logp_b, adv, ret)
         stats["mean_step_reward"] = rew.reshape(rew.shape[0], self.members, self.n_member).mean(dim=(0, 2)).tolist()
+        if self.objective is not None:
+            stats["objective_terms"] = self.objective.report()["terms"]
         if self.track_episodes:
             stats["episodes"], stats["mean_episode_return"], stats["mean_episode_length"] = self._episode_stats()
         return stats
@@ -1175,7 +1239,8 @@ class PopulationPPO(_Trainer):
         scores=None (track_episodes only): the ledger's mean finished-episode return since the last such call, read on the device
         (a member without a finished episode scores NaN: last); the ledger's totals are cleared afterwards.
         The draws are Philox's of (seed, self.generation, member): a run repeats and resumes bit for bit.  With rng="philox" the
-        learners' keys stay with their slots: a replaced member takes its parent's weights and goes on with its own stream.  Returns (parent, rank)
+        learners' keys stay with their slots: a replaced member takes its parent's weights and goes on with its own stream; so do the
+        objectives' weights (section 27).  Returns (parent, rank)
         as device int32 tensors -- parent[m] == m for a member that was not replaced -- without synchronising.  The host mirror
         hyper_rows is stale from here on (None): hypers() reads the rows back."""
         if not 0.0 <= frac <= 0.5:
@@ -1185,6 +1250,9 @@ class PopulationPPO(_Trainer):
         if own:
             if not self.track_episodes:
                 raise ValueError("evolve: scores=None takes the episode ledger's mean episode return: PopulationPPO(track_episodes=True)")
+            if self.objective is not None and not self.objective.uniform():
+                raise ValueError("evolve: scores=None ranks the members by their episode returns, and returns under different objectives "
+                                 "do not rank: pass scores (for instance the ledger's channel \"reward\": self.ledger.scores(\"reward\"))")
             scores = self.ledger.scores()
         score = torch.as_tensor(scores).detach().to(device=dev, dtype=torch.float64).reshape(-1).contiguous()
         if score.numel() != self.members:
